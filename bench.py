@@ -7,18 +7,27 @@ its own batch of 32; ranks exchange gradients once per step (RCCL all-reduce, ta
 ``--workload asr`` runs BASELINE configs[1] instead (audio-only 12-layer Branchformer + CTC + decoder, same batch).
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs bench_out/outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
+A plain run sets the step up, warms it up, times K steps and prints ONE JSON line on rank 0: metric, value, unit,
+higher_is_better, dtype, ms_per_step (the milliseconds one timed step took), the step's configuration, and
+rccl_world, dist_world, dist_backend, hbm_peak_gb_per_rank - which exchange really ran (ranks of the C ABI's RCCL
+communicator, 0 = none) and every rank's peak device memory: the first things to read on an N > 1 line.
+``--dump-outputs DIR`` writes what the last timed step computed (the loss and the parameter gradients a caller of the step
+receives) as DIR/<name>.npy; the inputs and weights are seeded, so two builds given the same arguments can be compared
+output for output.  ``--full`` adds every other measurement to the line, each taken outside the timed steps:
+  sustained    - the same step for --sustain-s seconds more (default 12 under --full);
+  eager        - the same step as eager launches, taken before the capture (1 GPU);
+  grad_exchange_exposed_ms_per_step - N > 1 or --force-rccl: the exchange's stream time that nothing hides;
   box          - in-process calibration of THIS device before the model is built (fp32 MFMA microbench, HBM copy);
   asr          - BASELINE configs[1] (the audio-only step) under the same protocol, so the driver's record holds it too (with its own
                  CPU figure);
   decode       - BASELINE configs[4] (beam 10 + 16 x 512 LM on the AV model): batch-1 p50 RTF over 8 utterances of 4 s and batch-64
                  utterances/s over 128, taken by a child `bench_decode.py --driver-record` BEFORE this process touches the GPU (a second HIP
                  context on the device, even an idle one, costs a batch-1 search 11 - 19 % per token);
-  rccl_world, dist_world, dist_backend, hbm_peak_gb_per_rank - which exchange really ran (ranks of the C ABI's RCCL communicator,
-                 0 = none) and every rank's peak device memory: the first things to read on an N > 1 line;
   fwd_encoder  - north_star's forward target (12-layer Branchformer forward, batch 32);
   roofline     - the dominant kernel (fp32 MFMA GEMM instantiation with the largest total time): algorithmic
                  FLOPs / HIP-event launch durations, measured in a separate instrumented replay of the same step;
@@ -392,6 +401,31 @@ def bench_asr_step(dev, steps=20, warmup=5):
     return out
 
 
+DUMP_SAMPLE = 1 << 23       # gradient entries kept by --dump-outputs (32 MB of float32)
+
+
+def dump_outputs(out_dir, loss, params):
+    """What one step hands its caller, as float32 / float64 .npy files (about 32 MB in all):
+      loss.npy        - the step's loss (float32, shape (1,));
+      grad_norm.npy   - the L2 norm of every parameter's gradient, in model.parameters() order (float64);
+      grad_sample.npy - every parameter's gradient flattened and concatenated in that order, all of it when it holds at most
+                        DUMP_SAMPLE entries, else the entries at DUMP_SAMPLE fixed positions (ascending, drawn with seed 0).
+    A parameter without a gradient counts as zeros of its size, so the positions stay aligned between builds."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    grads = [(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params]
+    flat = torch.cat(grads).float()
+    if flat.numel() > DUMP_SAMPLE:
+        idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[idx.to(flat.device)]
+    arrays = {"loss": loss.detach().float().reshape(1).cpu().numpy(),
+              "grad_norm": torch.stack([g.double().norm() for g in grads]).cpu().numpy(),
+              "grad_sample": flat.cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -418,10 +452,19 @@ def main():
     ap.add_argument("--no-box", action="store_true", help="skip the `box` calibration object (fp32 MFMA microbench, HBM copy)")
     ap.add_argument("--workload", choices=("asr", "avsr"), default="avsr",
                     help="asr: BASELINE configs[1] (headline); avsr: configs[2] tailored AV-Branchformer incl. the visual frontend")
-    ap.add_argument("--sustain-s", type=float, default=12.0,
+    ap.add_argument("--sustain-s", type=float, default=None,
                     help="after the timed steps keep stepping for this many seconds more and report that rate as `sustained` "
-                         "(clocks settle within a few seconds of MFMA-dense load); 0 = off")
+                         "(clocks settle within a few seconds of MFMA-dense load); 0 = off; default 12 with --full, else 0")
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline (box, eager, sustained, exposed exchange, roofline, "
+                         "fwd_encoder, asr, decode, cpu_baseline; the --no-* options still drop single ones)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's loss and parameter gradients to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if args.sustain_s is None:
+        args.sustain_s = 12.0 if args.full else 0.0
     global WORKLOAD, DROPOUT
     WORKLOAD = args.workload
     DROPOUT = not args.no_dropout
@@ -442,8 +485,8 @@ def main():
         raise SystemExit(subprocess.call(cmd, env=env))
 
     decode_obj = None
-    if (args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and WORKLOAD == "avsr" and args.mode == "step" and not args.no_decode
-            and not args.no_fwd_encoder):
+    if (args.full and args.gpus == 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1 and WORKLOAD == "avsr" and args.mode == "step"
+            and not args.no_decode and not args.no_fwd_encoder):
         # BASELINE configs[4] on the driver's record (replicas only; nothing to scale here), taken by a CHILD process BEFORE this process
         # touches the GPU.  A batch-1 search is a chain of ~140 dependent launches per token; it runs 11 - 19 % slower per token when a second
         # process holds a HIP context on the same GPU, idle or not (scripts/decode_after_load_probe.sh: 632 us per token alone, 693 beside an
@@ -474,7 +517,7 @@ def main():
                               "fwd_encoder": bench_fwd_encoder(dev, args.steps, args.warmup)}), flush=True)
         return
 
-    box = box_calibration(dev) if (rank == 0 and not args.no_box) else None      # before the model exists: the box, not the code
+    box = box_calibration(dev) if (args.full and rank == 0 and not args.no_box) else None      # before the model exists: the box, not the code
     if world > 1:
         torch.distributed.barrier()
     torch.manual_seed(0)
@@ -509,7 +552,7 @@ def main():
     # (1 GPU only: with N ranks the un-captured loop is measured by --no-graph; running hook-driven exchanges in front of the
     # capture made the gloo rehearsal's captured steps slower from step to step - 0.2 s, 1.7 s, 5.5 s of host time in the
     # exchange - so the N > 1 line keeps the order that was rehearsed: capture first, nothing before it)
-    if not args.no_graph and not args.no_eager and world == 1:
+    if args.full and not args.no_graph and not args.no_eager and world == 1:
         # the same step as eager launches (what a ragged, un-captured training loop pays): reported beside the graph number.
         # Taken BEFORE the capture, in the allocator / interpreter state a training loop would run in.
         n_eager = max(3, args.steps // 4)
@@ -586,6 +629,7 @@ def main():
                 static_loss.backward()
 
     trace = os.environ.get("TAVSR_BENCH_TRACE") == "1"     # diagnostic: synchronous per-phase times of every step on stderr
+    last = {"loss": static_loss}      # the loss of the latest step (eager: kept without its autograd graph)
 
     def step():
         t0 = time.perf_counter()
@@ -596,7 +640,7 @@ def main():
                 graph_b.replay()
         else:
             buckets.begin_step()       # the hooks enqueue buckets under the backward pass
-            fwd_bwd()
+            last["loss"] = fwd_bwd().detach()
         if trace:
             if os.environ.get("TAVSR_BENCH_TRACE_SYNC", "1") == "1":
                 torch.cuda.synchronize()
@@ -616,6 +660,8 @@ def main():
         step()
     barrier()
     elapsed = max_over_ranks(time.perf_counter() - t0)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last["loss"], params)      # (N > 1: the gradients after the exchange)
 
     sustained = None
     if args.sustain_s > 0:
@@ -631,7 +677,7 @@ def main():
                      "ms_per_step": round(1e3 * el_s / n_sus, 3), "seconds": round(el_s, 2),
                      "note": "same step, run back to back right after the timed region"}
     exposed_ms = None
-    if world > 1 or dp.FORCE_WORLD1:
+    if args.full and (world > 1 or dp.FORCE_WORLD1):
         # stream time of the exchange that nothing hides (pack + all-reduce + unpack behind the last gradient): a few steps
         # with one event pair each, outside the timed region
         pairs = []
@@ -694,7 +740,7 @@ def main():
         out["eager"] = eager_out
 
     buckets.overlap = False       # the legs below run on rank 0 alone: no collective may leave from a hook
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         # Instrumented eager replay of the same step: HIP events around every tavsr_gemm launch on the launch stream.
         prof = ops.GemmProfile()
         ops.PROFILE = prof
@@ -719,7 +765,7 @@ def main():
             "by_kernel": {k: {"calls_per_step": v["calls"] // nprof, "ms_per_step": round(1e3 * v["seconds"] / nprof, 3),
                               "tflops": round(v["flops"] / v["seconds"] / 1e12, 2)} for k, v in summ.items()},
         }
-    if rank == 0 and world == 1 and not args.no_fwd_encoder:
+    if args.full and rank == 0 and world == 1 and not args.no_fwd_encoder:
         del graph, graph_b, static_loss
         for p in params:
             p.grad = None
@@ -732,7 +778,7 @@ def main():
         out["decode"] = decode_obj
     if box is not None:
         out["box"] = box
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline()
         if "asr" in out:
             out["asr"]["cpu_baseline"] = cpu_baseline(budget_s=8.0, workload="asr", bs=4)

@@ -1,13 +1,15 @@
 """TEST INFRASTRUCTURE ONLY - writes tests/golden/wer_cases.json: synthetic "reference#hypothesis" files and what the
 reference's OWN evaluator (oracle/_ref/tasas, tasasIntervalo = src/evaluation/tasas/*.c compiled by oracle/Makefile)
 prints for them with the options of src/evaluation/bootstrap_wer.py:4-11.  Run here (needs /root/reference):
-    make -C oracle ref && python -m oracle.gen_golden_wer"""
+    make -C oracle ref && python -m oracle.gen_golden_wer
+``python -m oracle.gen_golden_wer fresh`` writes tests/golden/wer_fresh.json instead (see fresh())."""
 from __future__ import annotations
 
 import json
 import os
 import random
 import subprocess
+import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,5 +77,30 @@ def main():
         print(c["seed"], c["wer"], c["wer_counts"], c["wer_interval"], c["cer"], c["cer_counts"], c["cer_interval"])
 
 
+def fresh_text():
+    """the short-word file of tests/test_wer.py::test_oracle_equals_the_compiled_reference_on_fresh_files"""
+    rng = random.Random(9)
+    words = ["a", "bb", "ccc", "dd", "e", "ñu", "zz"]
+    lines = []
+    for _ in range(60):
+        r = [rng.choice(words) for _ in range(rng.randint(1, 9))]
+        h = [rng.choice(words) for _ in range(rng.randint(0, 9))]
+        lines.append(" ".join(r) + "#" + " ".join(h))
+    return "\n".join(lines) + "\n"
+
+
+def fresh():
+    """writes tests/golden/wer_fresh.json: that file and the rates `tasas -ie` prints for it (word and character mode)"""
+    text = fresh_text()
+    with tempfile.NamedTemporaryFile("w", suffix=".inf", delete=False, encoding="utf-8") as f:
+        f.write(text)
+        path = f.name
+    case = {"text": text, "wer": float(run("tasas", path, True)), "cer": float(run("tasas", path, False))}
+    os.unlink(path)
+    dst = os.path.join(ROOT, "tests", "golden", "wer_fresh.json")
+    json.dump(case, open(dst, "w"), ensure_ascii=False, indent=0)
+    print(case["wer"], case["cer"])
+
+
 if __name__ == "__main__":
-    main()
+    fresh() if sys.argv[1:] == ["fresh"] else main()

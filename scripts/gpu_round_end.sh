@@ -1,10 +1,13 @@
 # round-end records: default bench (AV) + ASR bench, forward-encoder bench, kernel tables, per-shape GEMM tables, PMC passes
 # (HBM bytes, MFMA utilisation), decode bench.  usage: bash scripts/gpu_round_end.sh   (outputs under gpurun_out/)
 mkdir -p gpurun_out
-( time timeout 900 python bench.py ) > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err; echo "default rc=$?"; tail -4 gpurun_out/bench_default.err
-cut -c1-330 gpurun_out/bench_default.json
-timeout 900 python bench.py --workload asr --steps 20 --warmup 5 > gpurun_out/bench_asr.json 2> gpurun_out/bench_asr.err; echo "asr rc=$?"
-cut -c1-300 gpurun_out/bench_asr.json
+# the two full bench lines (every leg: --full) go to $OUT_DIR (default bench_out/)
+OUT_DIR=${OUT_DIR:-bench_out}
+mkdir -p "$OUT_DIR"
+( time timeout 900 python bench.py --full ) > "$OUT_DIR/bench_default.json" 2> "$OUT_DIR/bench_default.err"; echo "default rc=$?"; tail -4 "$OUT_DIR/bench_default.err"
+cut -c1-330 "$OUT_DIR/bench_default.json"
+timeout 900 python bench.py --full --workload asr --steps 20 --warmup 5 > "$OUT_DIR/bench_asr.json" 2> "$OUT_DIR/bench_asr.err"; echo "asr rc=$?"
+cut -c1-300 "$OUT_DIR/bench_asr.json"
 timeout 600 python profiles/gemm_shapes.py --workload avsr > gpurun_out/gemm_shapes_av.txt 2>&1; echo "shapes av rc=$?"
 timeout 600 python profiles/gemm_shapes.py --workload asr > gpurun_out/gemm_shapes_asr.txt 2>&1; echo "shapes asr rc=$?"
 bash scripts/gpu_prof.sh | tail -3; cp gpurun_out/prof_stats.txt gpurun_out/kernel_stats_av.txt

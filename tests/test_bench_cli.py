@@ -60,3 +60,30 @@ def test_bench_line_reports_the_communicator_and_every_ranks_peak_memory():
         rep = ret[r]
         assert rep["rccl_world"] == 0 and rep["dist_world"] == 2 and rep["dist_backend"] == "gloo"
         assert rep["hbm_peak_gb_per_rank"] == [1.0, 2.0]
+
+
+def test_dump_outputs_writes_the_steps_loss_and_a_fixed_gradient_sample(tmp_path, monkeypatch):
+    """--dump-outputs: float32 / float64 .npy files only, the same positions of the concatenated gradients on every call,
+    and a parameter without a gradient counted as zeros so that the positions of the others do not move."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    bench = importlib.import_module("bench")
+    monkeypatch.setattr(bench, "DUMP_SAMPLE", 64)
+    torch.manual_seed(0)
+    lin = torch.nn.Linear(12, 10)
+    unused = torch.nn.Parameter(torch.ones(5))
+    loss = lin(torch.randn(3, 12)).square().sum()
+    loss.backward()
+    params = list(lin.parameters()) + [unused]
+    for d in ("a", "b"):
+        assert bench.dump_outputs(str(tmp_path / d), loss, params) == ["grad_norm", "grad_sample", "loss"]
+    got = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in ("loss", "grad_norm", "grad_sample")}
+    assert {n: a.dtype for n, a in got.items()} == {"loss": np.float32, "grad_norm": np.float64, "grad_sample": np.float32}
+    assert got["loss"].shape == (1,) and abs(float(got["loss"][0]) - float(loss)) < 1e-6
+    flat = torch.cat([lin.weight.grad.reshape(-1), lin.bias.grad, torch.zeros(5)])
+    assert np.allclose(got["grad_norm"], [float(lin.weight.grad.norm()), float(lin.bias.grad.norm()), 0.0])
+    idx = torch.randint(flat.numel(), (64,), generator=torch.Generator().manual_seed(0)).sort().values
+    assert np.array_equal(got["grad_sample"], flat[idx].numpy())
+    for n, a in got.items():
+        assert np.array_equal(np.load(tmp_path / "b" / f"{n}.npy"), a)

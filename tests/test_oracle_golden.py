@@ -5,7 +5,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TOKENS_EN, asr_conf, golden, max_rel, rel_err
+from helpers import TOKENS_EN, asr_conf, golden, grad_ok, max_rel, rel_err
 from oracle import leaves as L
 from oracle.model import (BranchformerEncoderOracle, CTCOracle, build_asr_oracle, compact,
                           fill_parameters_, synth)
@@ -53,7 +53,8 @@ def test_layer_matches_reference(tag, kw):
     assert rel_err(x.grad, g["grad_x"]) < 1e-4
     for n, p in layer.named_parameters():
         if "g_" + n in g.files:
-            assert rel_err(compact(p.grad), g["g_" + n]) < 1e-4, n
+            # (grad_ok: the analytically-zero linear_k.bias gradient is rounding noise on both sides, which differs between CPUs)
+            assert grad_ok(compact(p.grad), g["g_" + n], 1e-4), n
     if tag == "learned":
         assert rel_err(layer.weight_global, g["weight_global"]) < 1e-5
 
