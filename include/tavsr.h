@@ -28,7 +28,11 @@ extern "C" {
 typedef void* tavsr_stream_t; /* hipStream_t */
 
 enum { TAVSR_OK = 0, TAVSR_EINVAL = -1, TAVSR_EALIGN = -2, TAVSR_EUNSUPPORTED = -3 };
-enum { TAVSR_ACT_NONE = 0, TAVSR_ACT_RELU = 1, TAVSR_ACT_SWISH = 2, TAVSR_ACT_GELU = 3 };
+enum { TAVSR_ACT_NONE = 0, TAVSR_ACT_RELU = 1, TAVSR_ACT_SWISH = 2, TAVSR_ACT_GELU = 3,
+       /* the rest of espnet get_activation's set (src/encoder/branchformer/encoder.py:206, audiovisual/tailored/encoder.py:99:
+        * ffn_activation_type): torch.nn.Tanh, Hardtanh(-1, 1), SELU (scale 1.0507009873554805, alpha 1.6732632423543772);
+        * derivatives at the kinks as torch autograd takes them: hardtanh' = 0 at |z| >= 1, selu'(0) = scale * alpha */
+       TAVSR_ACT_TANH = 4, TAVSR_ACT_HARDTANH = 5, TAVSR_ACT_SELU = 6 };
 
 int tavsr_version(void);                     /* ABI version, bumped on any signature change */
 const char* tavsr_last_error_string(void);   /* host string, thread-local */

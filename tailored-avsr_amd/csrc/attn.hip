@@ -288,6 +288,7 @@ extern "C" int tavsr_axpby2d(const float* x, int64_t ldx, const float* y, int64_
 extern "C" int tavsr_act_bwd(const float* dh, const float* z, float* dz, int64_t n, int32_t act,
                              tavsr_stream_t stream) {
   TAVSR_REQUIRE(dh && z && dz, TAVSR_EINVAL, "act_bwd: null pointer");
+  TAVSR_REQUIRE(act_base_ok(act), TAVSR_EUNSUPPORTED, "act_bwd: activation %d is not among this launch's", act);
   TAVSR_REQUIRE(al16(dh) && al16(z) && al16(dz), TAVSR_EALIGN, "act_bwd: 16-byte alignment required");
   if (n <= 0) return TAVSR_OK;
   hipLaunchKernelGGL(act_bwd_kernel, dim3(cdiv(cdiv(n, 4), 256)), dim3(256), 0, (hipStream_t)stream, dh, z, dz, n, act);

@@ -129,6 +129,71 @@ __device__ __forceinline__ float act_bwd(int act, float z) {
   }
 }
 
+// tanh, hardtanh and SELU (TAVSR_ACT_TANH ..): the rest of espnet get_activation's set, for the encoders' feed-forward blocks.
+// NOT cases of act_fwd / act_bwd above: a wider run-time switch costs registers (and occupancy) in every kernel that takes the
+// activation at run time; these are instantiated where they are used (the streaming FFN kernels' template argument, the GEMM's
+// stand-alone epilogue for them).  Same hardware transcendentals.  Near 0 the closed forms cancel (1 - 2 / (e^2z + 1) and
+// e^z - 1 keep ~4 significant digits at |z| = 1e-3), so |z| < 1/4 takes short Taylor series instead (truncation < 1e-8
+// relative); above that the cancellation costs at most 2 bits.  tanh' = r (2 - r) with r = 1 - tanh|z| = 2 / (e^2|z| + 1) has
+// no cancellation where tanh saturates.  Derivatives at the kinks as torch autograd takes them: hardtanh' = 0 at |z| >= 1,
+// selu'(0) = scale * alpha (elu_backward: the negative branch at z <= 0).
+constexpr float kSeluScale = 1.0507009873554805f, kSeluAlpha = 1.6732632423543772f;
+__device__ __forceinline__ float tanh_small(float z) {      // |z| < 1/4: z - z^3/3 + 2z^5/15 - 17z^7/315 + 62z^9/2835
+  const float z2 = z * z;
+  return fmaf(z * z2, fmaf(z2, fmaf(z2, fmaf(z2, 0.021869488536155203f, -0.053968253968253971f), 0.13333333333333333f),
+                           -0.33333333333333333f), z);
+}
+__device__ __forceinline__ float tanh_rest(float az) {      // 1 - tanh|z|
+  return 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * az));
+}
+__device__ __forceinline__ float tanh_fast(float z) {
+  const float az = fabsf(z);
+  return az < 0.25f ? tanh_small(z) : copysignf(1.f - tanh_rest(az), z);
+}
+__device__ __forceinline__ float dtanh_fast(float z) {
+  const float az = fabsf(z);
+  if (az < 0.25f) {
+    const float t = tanh_small(z);
+    return fmaf(-t, t, 1.f);
+  }
+  const float r = tanh_rest(az);
+  return r * (2.f - r);
+}
+__device__ __forceinline__ float hardtanh_fwd(float z) { return z < -1.f ? -1.f : (z > 1.f ? 1.f : z); }
+__device__ __forceinline__ float hardtanh_bwd(float z) { return (z <= -1.f || z >= 1.f) ? 0.f : 1.f; }
+__device__ __forceinline__ float selu_fast(float z) {
+  if (z > 0.f) return kSeluScale * z;
+  const float em1 = z > -0.25f      // e^z - 1
+      ? z * fmaf(z, fmaf(z, fmaf(z, fmaf(z, fmaf(z, fmaf(z, 1.9841269841269841e-4f, 1.3888888888888889e-3f),
+                                                      8.3333333333333333e-3f), 4.1666666666666667e-2f), 0.16666666666666667f),
+                         0.5f), 1.f)
+      : __builtin_amdgcn_exp2f(1.4426950408889634f * z) - 1.f;
+  return (kSeluScale * kSeluAlpha) * em1;
+}
+__device__ __forceinline__ float dselu_fast(float z) {
+  return z <= 0.f ? (kSeluScale * kSeluAlpha) * __builtin_amdgcn_exp2f(1.4426950408889634f * z) : kSeluScale;
+}
+inline bool act_is_ext(int act) { return act == TAVSR_ACT_TANH || act == TAVSR_ACT_HARDTANH || act == TAVSR_ACT_SELU; }
+// kernels with the run-time switch above take these codes only (the library refuses the others there: nothing is launched)
+inline bool act_base_ok(int act) { return act >= TAVSR_ACT_NONE && act <= TAVSR_ACT_GELU; }
+// every code: for the kernels instantiated for the new ones
+__device__ __forceinline__ float act_fwd_all(int act, float z) {
+  switch (act) {
+    case TAVSR_ACT_TANH: return tanh_fast(z);
+    case TAVSR_ACT_HARDTANH: return hardtanh_fwd(z);
+    case TAVSR_ACT_SELU: return selu_fast(z);
+    default: return act_fwd(act, z);
+  }
+}
+__device__ __forceinline__ float act_bwd_all(int act, float z) {
+  switch (act) {
+    case TAVSR_ACT_TANH: return dtanh_fast(z);
+    case TAVSR_ACT_HARDTANH: return hardtanh_bwd(z);
+    case TAVSR_ACT_SELU: return dselu_fast(z);
+    default: return act_bwd(act, z);
+  }
+}
+
 // Philox4x32-10 counter-based generator (dropout masks, bootstrap resampling)
 __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
                                               uint32_t (&out)[4]) {

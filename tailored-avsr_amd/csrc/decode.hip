@@ -898,6 +898,7 @@ using namespace tavsr;
 
 extern "C" int tavsr_act_fwd(const float* x, float* y, int64_t n, int32_t act, tavsr_stream_t stream) {
   TAVSR_REQUIRE((x && y) || n <= 0, TAVSR_EINVAL, "act_fwd: null pointer");
+  TAVSR_REQUIRE(act_base_ok(act), TAVSR_EUNSUPPORTED, "act_fwd: activation %d is not among this launch's", act);
   if (n <= 0) return TAVSR_OK;
   hipLaunchKernelGGL(act_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, n, act);
   TAVSR_LAUNCH_CHECK();

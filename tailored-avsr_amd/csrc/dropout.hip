@@ -137,6 +137,7 @@ extern "C" int tavsr_dropout_add(const float* a, const float* t, float* y, int64
 extern "C" int tavsr_dropout_act_bwd(const float* dh, const float* z, float* dz, int64_t n, float p, int32_t act,
                                      const uint64_t* seed_dev, uint64_t offset, tavsr_stream_t stream) {
   TAVSR_REQUIRE((dh && z && dz && seed_dev) || n <= 0, TAVSR_EINVAL, "dropout_act_bwd: null pointer");
+  TAVSR_REQUIRE(act_base_ok(act), TAVSR_EUNSUPPORTED, "dropout_act_bwd: activation %d is not among this launch's", act);
   TAVSR_REQUIRE(p >= 0.f && p < 1.f, TAVSR_EINVAL, "dropout_act_bwd: p must be in [0, 1)");
   TAVSR_REQUIRE(offset % 4 == 0, TAVSR_EALIGN, "dropout_act_bwd: offset must be a multiple of 4");
   if (n <= 0) return TAVSR_OK;

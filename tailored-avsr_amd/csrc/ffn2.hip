@@ -78,7 +78,15 @@ __device__ __forceinline__ int rho(int r) { return (r & 3) + 8 * (r >> 2); }
 template <int ACT>
 __device__ __forceinline__ float act_fast(float z) {
   if (ACT == TAVSR_ACT_SWISH) return z * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
+  if (ACT == TAVSR_ACT_TANH) return tanh_fast(z);
+  if (ACT == TAVSR_ACT_HARDTANH) return hardtanh_fwd(z);
+  if (ACT == TAVSR_ACT_SELU) return selu_fast(z);
   return z > 0.f ? z : 0.f;
+}
+// the activations the chain kernels are instantiated for (espnet get_activation's set, encoder.py:206)
+inline bool ffn2_act_ok(int act) {
+  return act == TAVSR_ACT_RELU || act == TAVSR_ACT_SWISH || act == TAVSR_ACT_TANH || act == TAVSR_ACT_HARDTANH ||
+         act == TAVSR_ACT_SELU;
 }
 template <int N>
 __device__ __forceinline__ void vmwait() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
@@ -414,6 +422,9 @@ __device__ __forceinline__ float dact_fast(float z) {
     const float s = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * z));
     return s * (1.f + z * (1.f - s));
   }
+  if (ACT == TAVSR_ACT_TANH) return dtanh_fast(z);
+  if (ACT == TAVSR_ACT_HARDTANH) return hardtanh_bwd(z);
+  if (ACT == TAVSR_ACT_SELU) return dselu_fast(z);
   return z > 0.f ? 1.f : 0.f;
 }
 
@@ -730,6 +741,21 @@ void launch_fwd(const Ffn2Args& a, bool save, bool drop, hipStream_t s) {
   else if (drop) hipLaunchKernelGGL((ffn2_fwd_kernel<NS, false, true, ACT>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((ffn2_fwd_kernel<NS, false, false, ACT>), grid, dim3(256), 0, s, a);
 }
+template <int NS>
+void launch_fwd_act(int act, const Ffn2Args& a, bool save, bool drop, hipStream_t s) {
+  switch (act) {
+    case TAVSR_ACT_RELU: launch_fwd<NS, TAVSR_ACT_RELU>(a, save, drop, s); break;
+    case TAVSR_ACT_SWISH: launch_fwd<NS, TAVSR_ACT_SWISH>(a, save, drop, s); break;
+    case TAVSR_ACT_TANH: launch_fwd<NS, TAVSR_ACT_TANH>(a, save, drop, s); break;
+    case TAVSR_ACT_HARDTANH: launch_fwd<NS, TAVSR_ACT_HARDTANH>(a, save, drop, s); break;
+    default: launch_fwd<NS, TAVSR_ACT_SELU>(a, save, drop, s); break;
+  }
+}
+template <int ACT>
+void launch_bwd(const Ffn2Args& a, bool drop, dim3 grid, hipStream_t s) {
+  if (drop) hipLaunchKernelGGL((ffn2_bwd_kernel<true, ACT>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((ffn2_bwd_kernel<false, ACT>), grid, dim3(256), 0, s, a);
+}
 
 }  // namespace
 }  // namespace tavsr
@@ -751,7 +777,7 @@ extern "C" int tavsr_ffn2_fwd(const tavsr_ffn_desc* d, tavsr_stream_t stream) {
   TAVSR_REQUIRE(d, TAVSR_EINVAL, "ffn2_fwd: null descriptor");
   TAVSR_REQUIRE(d->M > 0 && d->D == 256 && d->N1 >= 1024 && d->N1 % 32 == 0, TAVSR_EUNSUPPORTED,
                 "ffn2_fwd: d_model 256 and a hidden size >= 1024 that is a multiple of 32 (got %d, %d)", d->D, d->N1);
-  TAVSR_REQUIRE(d->act == TAVSR_ACT_RELU || d->act == TAVSR_ACT_SWISH, TAVSR_EUNSUPPORTED, "ffn2_fwd: ReLU or Swish only");
+  TAVSR_REQUIRE(ffn2_act_ok(d->act), TAVSR_EUNSUPPORTED, "ffn2_fwd: ReLU, Swish, tanh, hardtanh or SELU only (got %d)", d->act);
   TAVSR_REQUIRE(d->x && d->ln_w && d->ln_b && d->w1 && d->b1 && d->w2 && d->b2 && d->y && d->ws, TAVSR_EINVAL, "ffn2_fwd: null operand");
   TAVSR_REQUIRE(al16(d->x) && al16(d->w1) && al16(d->w2) && al16(d->y) && al16(d->ws) && al16(d->ln_w) && al16(d->ln_b) &&
                     al16(d->b2) && d->ldx % 4 == 0 && (!d->res || (al16(d->res) && d->ldr % 4 == 0)),
@@ -776,16 +802,9 @@ extern "C" int tavsr_ffn2_fwd(const tavsr_ffn_desc* d, tavsr_stream_t stream) {
   if (const char* e = getenv("TAVSR_FFN2_DBG")) a.dbg = atoi(e);
   hipStream_t s = (hipStream_t)stream;
   const bool save = d->z != nullptr, drop = a.thr != 0;
-  if (p.NS == 5) {
-    if (d->act == TAVSR_ACT_RELU) launch_fwd<5, TAVSR_ACT_RELU>(a, save, drop, s);
-    else launch_fwd<5, TAVSR_ACT_SWISH>(a, save, drop, s);
-  } else if (p.NS == 4) {
-    if (d->act == TAVSR_ACT_RELU) launch_fwd<4, TAVSR_ACT_RELU>(a, save, drop, s);
-    else launch_fwd<4, TAVSR_ACT_SWISH>(a, save, drop, s);
-  } else {
-    if (d->act == TAVSR_ACT_RELU) launch_fwd<3, TAVSR_ACT_RELU>(a, save, drop, s);
-    else launch_fwd<3, TAVSR_ACT_SWISH>(a, save, drop, s);
-  }
+  if (p.NS == 5) launch_fwd_act<5>(d->act, a, save, drop, s);
+  else if (p.NS == 4) launch_fwd_act<4>(d->act, a, save, drop, s);
+  else launch_fwd_act<3>(d->act, a, save, drop, s);
   TAVSR_LAUNCH_CHECK();
   const float* res = d->res ? d->res : d->x;
   const int64_t ldr = d->res ? d->ldr : d->ldx;
@@ -801,7 +820,7 @@ extern "C" int tavsr_ffn2_bwd_dx(const float* dy, int64_t lddy, float alpha, con
                                  uint64_t offset_in, float* dz, float* dn, float* ws, int64_t ws_floats, tavsr_stream_t stream) {
   TAVSR_REQUIRE(M > 0 && D == 256 && N1 >= 1024 && N1 % 32 == 0, TAVSR_EUNSUPPORTED,
                 "ffn2_bwd_dx: d_model 256 and a hidden size >= 1024 that is a multiple of 32 (got %d, %d)", D, N1);
-  TAVSR_REQUIRE(act == TAVSR_ACT_RELU || act == TAVSR_ACT_SWISH, TAVSR_EUNSUPPORTED, "ffn2_bwd_dx: ReLU or Swish only");
+  TAVSR_REQUIRE(ffn2_act_ok(act), TAVSR_EUNSUPPORTED, "ffn2_bwd_dx: ReLU, Swish, tanh, hardtanh or SELU only (got %d)", act);
   TAVSR_REQUIRE(dy && w1 && w2 && z && dz && ws, TAVSR_EINVAL, "ffn2_bwd_dx: null operand");
   TAVSR_REQUIRE(al16(dy) && al16(w1) && al16(w2) && al16(z) && al16(dz) && al16(dn) && al16(ws) && lddy % 4 == 0, TAVSR_EINVAL,
                 "ffn2_bwd_dx: operands must be 16-byte aligned");
@@ -819,12 +838,12 @@ extern "C" int tavsr_ffn2_bwd_dx(const float* dy, int64_t lddy, float alpha, con
   hipStream_t s = (hipStream_t)stream;
   const bool drop = a.thr != 0;
   dim3 grid(a.G);
-  if (act == TAVSR_ACT_RELU) {
-    if (drop) hipLaunchKernelGGL((ffn2_bwd_kernel<true, TAVSR_ACT_RELU>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((ffn2_bwd_kernel<false, TAVSR_ACT_RELU>), grid, dim3(256), 0, s, a);
-  } else {
-    if (drop) hipLaunchKernelGGL((ffn2_bwd_kernel<true, TAVSR_ACT_SWISH>), grid, dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((ffn2_bwd_kernel<false, TAVSR_ACT_SWISH>), grid, dim3(256), 0, s, a);
+  switch (act) {
+    case TAVSR_ACT_RELU: launch_bwd<TAVSR_ACT_RELU>(a, drop, grid, s); break;
+    case TAVSR_ACT_SWISH: launch_bwd<TAVSR_ACT_SWISH>(a, drop, grid, s); break;
+    case TAVSR_ACT_TANH: launch_bwd<TAVSR_ACT_TANH>(a, drop, grid, s); break;
+    case TAVSR_ACT_HARDTANH: launch_bwd<TAVSR_ACT_HARDTANH>(a, drop, grid, s); break;
+    default: launch_bwd<TAVSR_ACT_SELU>(a, drop, grid, s); break;
   }
   TAVSR_LAUNCH_CHECK();
   if (!dn) return TAVSR_OK;      // the caller's LayerNorm backward sums the partials itself (tavsr_layernorm_bwd_partial_slab)

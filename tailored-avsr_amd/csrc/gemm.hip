@@ -1456,8 +1456,64 @@ static int64_t ws_floats_for(const tavsr_gemm_desc& d, int nsplit) {
   return (int64_t)nsplit * d.nb1 * d.nb2 * d.M * d.N + (d.a_rowsum ? (int64_t)nsplit * d.M : 0);
 }
 
+// Epilogue of the activations the GEMM kernels' switch does not hold (tanh / hardtanh / SELU, common.h): the product was stored
+// with its bias only (C, and Z); this applies act, act'(DZ), the dropout mask, alpha and the residual in the fused epilogue's
+// order and with its mask (word n & 3 of Philox counter drop_offset/4 + (m*N + n)/4).  One thread per 4 columns of a row.
+__global__ __launch_bounds__(256) void ext_epilogue_kernel(const tavsr_gemm_desc d) {
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+  if (i >= (int64_t)d.M * d.N) return;
+  const int m = (int)(i / d.N), n = (int)(i % d.N);
+  uint32_t keep[4] = {1u, 1u, 1u, 1u};
+  float inv_keep = 1.f;
+  if (d.drop_p > 0.f) {
+    const uint64_t sd = d.drop_seed[0], ctr = (d.drop_offset >> 2) + (uint64_t)(i >> 2);
+    const uint32_t thr = (uint32_t)((double)d.drop_p * 4294967296.0);
+    uint32_t w[4];
+    philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)sd, (uint32_t)(sd >> 32), w);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) keep[q] = w[q] >= thr;
+    inv_keep = 1.f / (1.f - d.drop_p);
+  }
+  float* c = d.C + (int64_t)m * d.ldc + n;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    float x = act_fwd_all(d.act, c[q]);
+    if (d.DZ) x *= act_bwd_all(d.dact, d.DZ[(int64_t)m * d.ldc + n + q]);
+    x = keep[q] ? x * inv_keep : 0.f;
+    x *= d.alpha;
+    if (d.R) x += d.R[(int64_t)m * d.ldr + n + q];
+    c[q] = x;
+  }
+}
+
+static int run(const tavsr_gemm_desc* dp, int force_cfg, int force_split, hipStream_t s);
+
+// act or dact among tanh / hardtanh / SELU: the product through the unchanged kernels with bias (and Z) only, then
+// ext_epilogue_kernel over C - one more pass over the result; the encoders' feed-forward blocks take it only off the
+// streaming route (csrc/ffn2.hip holds these activations in its own instantiations).
+static int run_ext(const tavsr_gemm_desc* dp, int force_cfg, int force_split, hipStream_t s) {
+  const tavsr_gemm_desc& d = *dp;
+  TAVSR_REQUIRE(d.nb1 * d.nb2 <= 1 && d.conv_mode == 0 && !d.a_rowsum && !d.rowstat && !g_ln_tail, TAVSR_EUNSUPPORTED,
+                "tavsr_gemm: tanh / hardtanh / SELU epilogues on plain unbatched products only (no row sums or statistics)");
+  TAVSR_REQUIRE((act_base_ok(d.act) || act_is_ext(d.act)) && (!d.DZ || act_base_ok(d.dact) || act_is_ext(d.dact)), TAVSR_EINVAL,
+                "tavsr_gemm: unknown activation %d / %d", d.act, d.dact);
+  TAVSR_REQUIRE(d.N % 4 == 0 && (!d.R || d.R != d.C) && (!d.DZ || d.DZ != d.C), TAVSR_EUNSUPPORTED,
+                "tavsr_gemm: tanh / hardtanh / SELU epilogues need N %% 4 == 0 and R, DZ apart from C");
+  TAVSR_REQUIRE(d.drop_p == 0.f || d.drop_seed, TAVSR_EINVAL, "tavsr_gemm: dropout needs a device seed");
+  if (d.M == 0 || d.N == 0) return TAVSR_OK;
+  tavsr_gemm_desc g = d;
+  g.act = g.dact = TAVSR_ACT_NONE;
+  g.DZ = nullptr; g.R = nullptr; g.alpha = 1.f; g.drop_p = 0.f; g.drop_seed = nullptr;
+  int rc = run(&g, force_cfg, force_split, s);
+  if (rc != TAVSR_OK) return rc;
+  hipLaunchKernelGGL(ext_epilogue_kernel, dim3(cdiv((int64_t)d.M * d.N / 4, 256)), dim3(256), 0, s, d);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
 static int run(const tavsr_gemm_desc* dp, int force_cfg, int force_split, hipStream_t s) {
   TAVSR_REQUIRE(dp != nullptr, TAVSR_EINVAL, "tavsr_gemm: null descriptor");
+  if (act_is_ext(dp->act) || (dp->DZ && act_is_ext(dp->dact))) return run_ext(dp, force_cfg, force_split, s);
   tavsr_gemm_desc d = *dp;
   TAVSR_REQUIRE(d.M >= 0 && d.N >= 0 && d.K >= 0, TAVSR_EINVAL, "tavsr_gemm: negative dims");
   if (d.nb1 <= 0) d.nb1 = 1;

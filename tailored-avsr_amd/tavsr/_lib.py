@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TAVSR_LIB selects another build of the same library (profiles/gemm_trace.py's instrumented one); never a fallback.
 LIB_PATH = os.environ.get("TAVSR_LIB") or os.path.join(_HERE, "lib", "libtavsr_hip.so")
 
-ACT = {None: 0, "none": 0, "relu": 1, "swish": 2, "gelu": 3}
+ACT = {None: 0, "none": 0, "relu": 1, "swish": 2, "gelu": 3, "tanh": 4, "hardtanh": 5, "selu": 6}
 
 
 class TavsrError(RuntimeError):

@@ -21,6 +21,8 @@ class AdaptiveAudioVisualFusion(torch.nn.Module):
         self.acoustic_branch_drop_rate = acoustic_branch_drop_rate
         if audiovisual_layer_type != "upsampling_positionwise":
             raise ValueError("Support only upsampling positionwise feed forward fusion.")
+        if activation_type not in ("relu", "swish"):      # the encoders' FFNs take espnet's whole set; this one keeps two
+            raise ValueError(f"unsupported activation on the HIP path: {activation_type}")
         self.merge_method = merge_method
         if merge_method == "learned_ave":
             self.acoustic_pooling_proj = torch.nn.Linear(input_size, 1)

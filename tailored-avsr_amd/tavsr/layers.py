@@ -38,9 +38,13 @@ class Linear(nn.Linear):
         return F_.LinearFn.apply(x, self.weight, self.bias, 1.0)
 
 
+# espnet get_activation's table (encoder.py:206 -> espnet2 nets_utils.get_activation): every member has its kernels
+FFN_ACTIVATIONS = ("hardtanh", "tanh", "relu", "selu", "swish")
+
+
 def get_activation_name(act) -> str:
     if isinstance(act, str):
-        if act not in ("relu", "swish"):
+        if act not in FFN_ACTIVATIONS:
             raise ValueError(f"unsupported activation on the HIP path: {act}")
         return act
     raise ValueError("activation must be given by name")

@@ -242,6 +242,9 @@ def linear_dx_drop(dy, w, tok, *, alpha=1.0, DZ=None, dact=None):
         out = empty(M, K, like=dy)
         gemm(M, K, N, dy, dy.stride(0), w, w.stride(0), out, K, b_kmajor=True, alpha=alpha, DZ=DZ, dact=dact, drop=tok)
         return out
+    if DZ is not None and ACT[dact] > ACT["gelu"]:      # tanh / hardtanh / SELU: act'(DZ) in the GEMM's epilogue, then the mask
+        dh = linear_dx(dy, w, alpha=alpha, DZ=DZ, dact=dact)
+        return dropout(dh, tok[0], out=dh, token=tok)[0]
     dh = linear_dx(dy, w, alpha=alpha)
     if DZ is not None:
         return dropout_act_bwd(dh, DZ, dact, tok, out=dh)
@@ -871,7 +874,7 @@ def ffn2_usable(x, w1, act) -> bool:
 def ffn2_shape_ok(x, w1, act) -> bool:
     return (x.dim() == 2 and x.shape[1] == 256 and w1.shape[0] >= 1024 and w1.shape[0] % 32 == 0
             and x.stride(1) == 1 and x.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and w1.is_contiguous()
-            and act in ("relu", "swish"))
+            and act in ("relu", "swish", "tanh", "hardtanh", "selu"))
 
 
 def ffn2_fwd(x, ln_w, ln_b, eps, w1, b1, w2, b2, act, scale, p=0.0, save=True, ln2=(), ln2_eps=1e-12, ln2_stats=False):
