@@ -690,6 +690,32 @@ int tavsr_ctc_greedy(const float* logits, int64_t ld_t, int64_t ld_b, const int6
                      tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mask-CTC decoding (src/models/maskctc_model.py:285-349, MaskCTCInference.forward), one workgroup per utterance,
+ * no host value read or written (a decode loop is one stream of launches, capturable).  Integer outputs: bit-exact contract.
+ *   maskctc_init: from the CTC logits (strides as ctc_greedy): per frame t < hlens[b] the argmax (ctc_greedy's rule) and
+ *                 p = 1 / sum_v exp(x_v - max) (:289); runs of equal ids (:290) with the maximum p of the run (:298-305);
+ *                 blank runs dropped (:291).  For the n kept tokens: y_hat[b,:n] the token, tok_prob[b,:n] its probability,
+ *                 y_in[b,:n] the token, or mask_token where (double)p < threshold (:311-320); positions n .. ld_y - 1 of
+ *                 the three rows are 0.  y_len[b] = n; plan[b] = {mask_num, num_iter, per_iter} with
+ *                 num_iter = n_iterations if mask_num >= n_iterations > 0 else mask_num (:326-327) and
+ *                 per_iter = mask_num / num_iter (:332; 0 when nothing is masked).  ld_y >= T is the row stride of
+ *                 y_in / y_hat / tok_prob.
+ *   maskctc_step: pass `it` of the fill loop on the decoder logits [B, L, V1] (V1 = V + 1 columns, the mask column
+ *                 competes; logits[b][l][v] at b*ld_b + l*ld_l + v).  Utterance b is left untouched when
+ *                 it >= num_iter[b].  Otherwise every position l < y_len[b] with y_in == mask_token gets its row maximum
+ *                 and argmax (torch.max order); in the last pass (it == num_iter[b] - 1, :339-340) all of them take their
+ *                 argmax, before that the min(per_iter[b], masked positions) with the highest maxima do (:331-334).
+ *                 Contract where torch.topk leaves the order open: equal maxima go to the lower position.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_maskctc_init(const float* logits, int64_t ld_t, int64_t ld_b, const int64_t* hlens, int32_t blank,
+                       int32_t mask_token, double threshold, int32_t n_iterations, int64_t* y_in, int64_t* y_hat,
+                       float* tok_prob, int64_t ld_y, int64_t* y_len, int32_t* plan, int32_t B, int32_t T, int32_t V,
+                       tavsr_stream_t stream);
+int tavsr_maskctc_step(const float* logits, int64_t ld_l, int64_t ld_b, int64_t* y_in, int64_t ld_y,
+                       const int64_t* y_len, const int32_t* plan, int32_t it, int32_t mask_token, int32_t B, int32_t L,
+                       int32_t V1, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Attention-decoder loss side (espnet LabelSmoothingLoss + th_accuracy, espnet_model.py:553-569)
  * and decoder input embedding (Embedding + PositionalEncoding, espnet transformer_decoder.py).
  *   lsm_loss: row_loss[r] = KL(smoothed one-hot || softmax(logits[r])) (0 for ignored rows),

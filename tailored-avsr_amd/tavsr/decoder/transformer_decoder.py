@@ -54,12 +54,20 @@ class TransformerDecoder(torch.nn.Module):
                                                    self.output_layer.bias]
         return P
 
-    def forward(self, hs_pad, hlens, ys_in_pad, ys_in_lens):
-        """hs_pad (B,T,D), hlens (B), ys_in_pad (B,L) int64, ys_in_lens (B) -> (logits (B,L,V), olens)."""
-        pe = self.embed[1].table(ys_in_pad.size(1), hs_pad.device)
+    def _cfg(self):
         cfg = dict(heads=self.heads, num_blocks=self.num_blocks)
         if self.training:    # (dropout_rate, positional, self-attention, source-attention) of the espnet2 decoder
             cfg.update(p=self._rates[0], p_pos=self._rates[1], p_self=self._rates[2], p_src=self._rates[3])
+        return cfg
+
+    def forward(self, hs_pad, hlens, ys_in_pad, ys_in_lens, memory_kv=None):
+        """hs_pad (B,T,D), hlens (B), ys_in_pad (B,L) int64, ys_in_lens (B) -> (logits (B,L,V), olens).
+        ``memory_kv``: the layers' source-attention key / value projections of ``hs_pad`` from an earlier call (decoding only: the
+        node refuses a backward pass through it)."""
+        pe = self.embed[1].table(ys_in_pad.size(1), hs_pad.device)
+        cfg = self._cfg()
+        if memory_kv is not None:
+            cfg["memory_kv"] = memory_kv
         logits = F_.grad_apply(F_.TransformerDecoderFn, hs_pad, hlens.to(torch.int64), ys_in_pad.to(torch.int64),
                                                ys_in_lens.to(torch.int64), pe, cfg, *self._params())
         return logits, ys_in_lens

@@ -1086,6 +1086,16 @@ class TransformerDecoderFn(torch.autograd.Function):
     output_layer.weight, output_layer.bias];  returns logits [B, L, V]."""
 
     @staticmethod
+    def project_memory(mem2, nb, D, P):
+        """kv_all [B T, nb * 2 D]: layer li's source-attention keys at columns 2 li D, values at (2 li + 1) D"""
+        kv_all = ops.empty(mem2.shape[0], nb * 2 * D, like=mem2)
+        kvp = [(P[1 + li * _NL + _DI[f"src_attn.linear_{c}.weight"]], P[1 + li * _NL + _DI[f"src_attn.linear_{c}.bias"]], (2 * li + j) * D)
+               for li in range(nb) for j, c in enumerate("kv")]
+        for i in range(0, len(kvp), 12):
+            ops.linear_group(mem2, kvp[i: i + 12], kv_all)
+        return kv_all
+
+    @staticmethod
     def forward(ctx, memory, hlens, ys_in, ys_lens, pe, cfg, *P):
         need = _note_ctx(ctx)
         B, T, D = memory.shape
@@ -1097,17 +1107,21 @@ class TransformerDecoderFn(torch.autograd.Function):
         mem2 = memory.reshape(B * T, D)
         emb_w = P[0]
         pd, ppos, pself, psrc = (cfg.get(k, 0.0) for k in ("p", "p_pos", "p_self", "p_src"))
+        causal = bool(cfg.get("causal", True))      # False: the MLM decoder's self-attention (key padding only, espnet2 mlm_decoder.py)
+        memory_kv = cfg.get("memory_kv")             # the layers' key / value projections of the memory, computed by an earlier call
+        if memory_kv is not None and need:
+            raise NotImplementedError("memory_kv is the decoding path: no backward pass through a hoisted projection")
         x = ops.embed_pe(ys_in.contiguous(), emb_w, pe, math.sqrt(D)).view(M, D)
         t_pos = _drop_(x, ppos)                              # PositionalEncoding dropout
         saved = []
         # the key / value projections of the encoder memory do not depend on the decoder's state: all layers' in grouped launches up front
         # (2400 tiles of M = B T rows) instead of one 200-tile launch inside every layer's chain; layer li reads its window of kv_all
         ldkv = nb * 2 * D
-        kv_all = ops.empty(B * T, ldkv, like=memory)
-        kvp = [(P[1 + li * _NL + _DI[f"src_attn.linear_{c}.weight"]], P[1 + li * _NL + _DI[f"src_attn.linear_{c}.bias"]], (2 * li + j) * D)
-               for li in range(nb) for j, c in enumerate("kv")]
-        for i in range(0, len(kvp), 12):
-            ops.linear_group(mem2, kvp[i: i + 12], kv_all)
+        if memory_kv is not None:
+            assert memory_kv.shape == (B * T, ldkv) and memory_kv.is_contiguous(), (memory_kv.shape, (B * T, ldkv))
+            kv_all = memory_kv
+        else:
+            kv_all = TransformerDecoderFn.project_memory(mem2, nb, D, P)
         for li in range(nb):
             p = lambda n, li=li: P[1 + li * _NL + _DI[n]]
             s = {}
@@ -1119,9 +1133,9 @@ class TransformerDecoderFn(torch.autograd.Function):
             fused = ops.ATTN_FUSED and dk == 64
             if fused:
                 tk_a = "fused"
-                cx, attn = _AttnFused.fwd(qkv, 0, qkv, D, qkv, 2 * D, B, L, L, H, dk, ys_lens, True, p_att=pself)
+                cx, attn = _AttnFused.fwd(qkv, 0, qkv, D, qkv, 2 * D, B, L, L, H, dk, ys_lens, causal, p_att=pself)
             else:
-                cx, attn, tk_a = _SelfAttnCore.fwd(qkv, 3 * D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, B, L, L, H, dk, ys_lens, True,
+                cx, attn, tk_a = _SelfAttnCore.fwd(qkv, 3 * D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, B, L, L, H, dk, ys_lens, causal,
                                                    p_att=pself)
             x1, tk_r = ops.linear_drop(cx, p("self_attn.linear_out.weight"), p("self_attn.linear_out.bias"), pd, res=x)   # x + dropout(self_attn(...))
             s["self"] = (x, m1, r1, n1, qkv, cx, attn, tk_a, tk_r)
@@ -1216,7 +1230,7 @@ class TransformerDecoderFn(torch.autograd.Function):
             dqkv = torch.empty_like(qkv)
             if tk_a == "fused":
                 _AttnFused.bwd(dcx, cx, attn, qkv, 0, qkv, D, qkv, 2 * D, dqkv, 0, dqkv, D, dqkv, 2 * D, B, L, L, H, dk,
-                               ctx.ys_lens, True)
+                               ctx.ys_lens, bool(ctx.cfg.get("causal", True)))
             else:
                 _SelfAttnCore.bwd(dcx, attn, qkv, 3 * D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, dqkv, 3 * D, 0, dqkv, 3 * D, D,
                                   dqkv, 3 * D, 2 * D, B, L, L, H, dk, tok=tk_a)

@@ -129,7 +129,7 @@ class ESPnetAVSRModel(ESPnetASRModel):
         ops.rng_step_begin(audio.device)
         text = cut_to_longest(text.to(torch.int64).masked_fill(text == -1, self.ignore_id), text_lengths)
         encoder_out, encoder_out_lens = self.encode(audio, audio_lengths, video, video_lengths)
-        return self._hybrid_loss(encoder_out, encoder_out_lens, text, text_lengths, batch_size)
+        return self._hybrid_loss(encoder_out, encoder_out_lens, text, text_lengths, batch_size, **kwargs)
 
     @torch.no_grad()
     def ctc_greedy(self, audio, audio_lengths, video, video_lengths):

@@ -198,10 +198,10 @@ class ESPnetASRModel(torch.nn.Module):
         ops.rng_step_begin(speech.device)    # fresh dropout masks for this step (a kernel: captured graphs replay it)
         text = cut_to_longest(text.to(torch.int64).masked_fill(text == -1, self.ignore_id), text_lengths)
         encoder_out, encoder_out_lens = self.encode(speech, speech_lengths)
-        return self._hybrid_loss(encoder_out, encoder_out_lens, text, text_lengths, batch_size)
+        return self._hybrid_loss(encoder_out, encoder_out_lens, text, text_lengths, batch_size, **kwargs)
 
     # CTC + attention losses and the stats dict: espnet_model.py:258-356 == avsr_espnet_model.py:253-367
-    def _hybrid_loss(self, encoder_out, encoder_out_lens, text, text_lengths, batch_size):
+    def _hybrid_loss(self, encoder_out, encoder_out_lens, text, text_lengths, batch_size, **kwargs):
         intermediate_outs = None
         if isinstance(encoder_out, tuple):
             encoder_out, intermediate_outs = encoder_out
@@ -233,7 +233,22 @@ class ESPnetASRModel(torch.nn.Module):
                     stats[f"cer_interctc_layer{layer_idx}"] = cer_ic
                 n_ic = len(intermediate_outs)
                 loss_ctc = F_.WeightedSumFn.apply(loss_ctc, loss_interctc, 1 - self.interctc_weight, self.interctc_weight / n_ic)
-        acc_att = cer_att = wer_att = None
+        loss_att, dec_stats = self._decoder_branch(encoder_out, encoder_out_lens, text, text_lengths, **kwargs)
+        br.join()
+        if self.ctc_weight == 0.0:
+            loss = loss_att
+        elif self.ctc_weight == 1.0:
+            loss = loss_ctc
+        else:
+            loss = F_.WeightedSumFn.apply(loss_ctc, loss_att, self.ctc_weight, 1 - self.ctc_weight)
+        stats.update(dec_stats)
+        stats["loss"] = loss.detach()
+        weight = torch.full((1,), batch_size, dtype=torch.long, device=loss.device)
+        return loss.view(1), stats, weight
+
+    # the decoder's loss and its stats entries (espnet_model.py:306-317, 332-336); the Mask-CTC models put their MLM branch here
+    def _decoder_branch(self, encoder_out, encoder_out_lens, text, text_lengths, **kwargs):
+        loss_att = acc_att = cer_att = wer_att = None
         if self.ctc_weight != 1.0:
             ys_in, ys_out = add_sos_eos(text, text_lengths, self.sos, self.eos, self.ignore_id)
             decoder_out, _ = self.decoder(encoder_out, encoder_out_lens, ys_in, text_lengths + 1)
@@ -243,18 +258,8 @@ class ESPnetASRModel(torch.nn.Module):
             if not self.training and self.error_calculator is not None:
                 ids, _, _ = ops.ctc_greedy(decoder_out.detach().contiguous(), None, -1, collapse=False)  # argmax(-1)
                 cer_att, wer_att = self.error_calculator(ids.cpu(), text.cpu())
-        br.join()
-        if self.ctc_weight == 0.0:
-            loss = loss_att
-        elif self.ctc_weight == 1.0:
-            loss = loss_ctc
-        else:
-            loss = F_.WeightedSumFn.apply(loss_ctc, loss_att, self.ctc_weight, 1 - self.ctc_weight)
-        stats["loss_att"] = loss_att.detach() if loss_att is not None else None
-        stats["acc"], stats["cer"], stats["wer"] = acc_att, cer_att, wer_att
-        stats["loss"] = loss.detach()
-        weight = torch.full((1,), batch_size, dtype=torch.long, device=loss.device)
-        return loss.view(1), stats, weight
+        return loss_att, {"loss_att": loss_att.detach() if loss_att is not None else None, "acc": acc_att, "cer": cer_att,
+                          "wer": wer_att}
 
     @torch.no_grad()
     def ctc_greedy(self, speech, speech_lengths):

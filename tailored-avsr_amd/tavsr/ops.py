@@ -1387,6 +1387,35 @@ def ctc_greedy(logits, hlens=None, blank=0, collapse=True):
     return ids, hyp, hl
 
 
+def maskctc_init(logits, hlens, blank, mask_token, threshold, n_iterations):
+    """CTC logits [B,T,V] -> (y_in, y_hat [B,max(T,1)] int64, tok_prob [B,max(T,1)], y_len [B] int64,
+    plan [B,3] int32 = (mask_num, num_iter, per_iter)): the start of MaskCTCInference.forward (tavsr_maskctc_init)."""
+    B, T, V = logits.shape
+    require_cuda(logits, hlens)
+    assert logits.is_contiguous() and logits.dtype == torch.float32
+    Lc = max(T, 1)
+    y_in = torch.empty((B, Lc), dtype=torch.int64, device=logits.device)
+    y_hat = torch.empty((B, Lc), dtype=torch.int64, device=logits.device)
+    tok_prob = empty(B, Lc, like=logits)
+    y_len = torch.empty((B,), dtype=torch.int64, device=logits.device)
+    plan = torch.empty((B, 3), dtype=torch.int32, device=logits.device)
+    check(lib().tavsr_maskctc_init(ptr(logits), C.c_int64(V), C.c_int64(T * V), ptr(hlens), int(blank), int(mask_token),
+                                   C.c_double(float(threshold)), int(n_iterations), ptr(y_in), ptr(y_hat), ptr(tok_prob),
+                                   C.c_int64(Lc), ptr(y_len), ptr(plan), B, T, V, stream()), "tavsr_maskctc_init")
+    return y_in, y_hat, tok_prob, y_len, plan
+
+
+def maskctc_step(logits, y_in, y_len, plan, it, mask_token):
+    """pass ``it`` of the Mask-CTC fill loop on decoder logits [B,L,V+1]; ``y_in`` [B,>=L] int64 is updated in place."""
+    B, L, V1 = logits.shape
+    require_cuda(logits, y_in, y_len, plan)
+    assert logits.is_contiguous() and logits.dtype == torch.float32 and y_in.dtype == torch.int64 and y_in.stride(1) == 1
+    assert y_len.dtype == torch.int64 and plan.dtype == torch.int32 and plan.is_contiguous() and y_in.shape[1] >= L
+    check(lib().tavsr_maskctc_step(ptr(logits), C.c_int64(V1), C.c_int64(L * V1), ptr(y_in), C.c_int64(y_in.stride(0)),
+                                   ptr(y_len), ptr(plan), int(it), int(mask_token), B, L, V1, stream()), "tavsr_maskctc_step")
+    return y_in
+
+
 def lsm_loss(logits2d, target, ignore, smoothing):
     rows, V = logits2d.shape
     require_cuda(logits2d, target)

@@ -5,20 +5,22 @@ from __future__ import annotations
 import argparse
 
 from ..ctc.ctc import CTC
+from ..decoder.mlm_decoder import MLMDecoder
 from ..decoder.transformer_decoder import TransformerDecoder
 from ..encoder.branchformer.encoder import MyBranchformerEncoder
 from ..frontend.conv3d_resnet18 import Conv3dResNet18
 from ..frontend.default import DefaultFrontend
 from ..models.espnet_model import ESPnetASRModel, UtteranceMVN
+from ..models.maskctc_model import MaskCTCModel
 from ..specaug.specaug import SpecAug
 from ..utils.tokens import load_token_list
 
 frontend_choices = {"default": DefaultFrontend, "conv3dresnet18": Conv3dResNet18}      # src/tasks/asr.py:93-103
 specaug_choices = {"specaug": SpecAug}
 encoder_choices = {"branchformer": MyBranchformerEncoder}
-decoder_choices = {"transformer": TransformerDecoder}
+decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder}
 normalize_choices = {"utterance_mvn": UtteranceMVN}
-model_choices = {"espnet": ESPnetASRModel}
+model_choices = {"espnet": ESPnetASRModel, "maskctc": MaskCTCModel}
 
 
 def _pick(table, name, what):

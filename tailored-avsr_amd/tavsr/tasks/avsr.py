@@ -6,6 +6,7 @@ import argparse
 
 from ..audiovisual_fusion.adaptive_audiovisual_fusion import AdaptiveAudioVisualFusion
 from ..ctc.ctc import CTC
+from ..decoder.mlm_decoder import MLMDecoder
 from ..decoder.transformer_decoder import TransformerDecoder
 from ..embedding_for_avsr.default import DefaultEmbeddingLayerForAVSR
 from ..encoder.audiovisual.conventional.encoder import ConventionalEncoder
@@ -13,6 +14,7 @@ from ..encoder.audiovisual.tailored.encoder import TailoredEncoder
 from ..frontend.conv3d_resnet18 import Conv3dResNet18
 from ..frontend.default import DefaultFrontend
 from ..models.avsr_espnet_model import ESPnetAVSRModel
+from ..models.avsr_maskctc_model import AVSRMaskCTCModel
 from ..models.espnet_model import UtteranceMVN
 from ..specaug.specaug import SpecAug
 from ..utils.tokens import load_token_list
@@ -25,9 +27,9 @@ acoustic_embed_choices = {"default": DefaultEmbeddingLayerForAVSR}
 visual_embed_choices = {"default": DefaultEmbeddingLayerForAVSR}
 encoder_choices = {"tailored": TailoredEncoder, "conventional": ConventionalEncoder}
 audiovisual_fusion_choices = {"adaptive": AdaptiveAudioVisualFusion}
-decoder_choices = {"transformer": TransformerDecoder}
+decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder}
 normalize_choices = {"utterance_mvn": UtteranceMVN}
-model_choices = {"espnet": ESPnetAVSRModel}
+model_choices = {"espnet": ESPnetAVSRModel, "maskctc": AVSRMaskCTCModel}
 
 
 class AVSRTask:
