@@ -1,6 +1,6 @@
 """What a dependent launch costs in a captured chain at the grids of a batch-1 search step (tavsr_probe_launch): nothing at all,
 one memory round trip + store, and that plus a barrier and a second dependent read.  The floor under tavsr_rowlin / tree attention."""
-import ctypes as C, os, sys, torch
+import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tailored-avsr_amd"))
 from tavsr._lib import addr, check, lib, stream
@@ -30,6 +30,6 @@ for grid, block in ((1, 64), (32, 256), (80, 64), (96, 512), (128, 512), (128, 1
         off = [0]
         def fn():
             off[0] = (off[0] + grid * block * 4 + 4096) % (buf.numel() - grid * block * 8)
-            check(lib().tavsr_probe_launch(kind, grid, block, C.c_void_p(addr(buf, off[0])), grid * block * 4, stream()), "probe")
+            check(lib().tavsr_probe_launch(kind, grid, block, addr(buf, off[0]), grid * block * 4, stream()), "probe")
         row.append(chain_us(fn))
     print(f"grid {grid:5d} x {block:4d} threads: empty {row[0]:5.2f} us   load+store {row[1]:5.2f} us   load, barrier, load, store {row[2]:5.2f} us", flush=True)

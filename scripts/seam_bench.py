@@ -1,7 +1,7 @@
 """a phase boundary inside one launch (grid barrier, XCD-hierarchical) against a launch boundary, at the shapes of a layer seam: 256
 workgroups, every one publishing 4 KB .. 128 KB that another one reads in the next phase (the feed-forward block's partial outputs are 128
 rows x 256 floats = 128 KB per workgroup).  us per boundary in a captured chain."""
-import ctypes as C, os, sys, torch
+import os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tailored-avsr_amd"))
 from tavsr._lib import addr, check, lib, stream
@@ -13,7 +13,7 @@ def timed(kind, per_wg, reps=100, shift=97, flags=0):
     kind = kind + 256 * (shift + 1) + (flags << 24)
     buf = torch.zeros(NPH * G * per_wg, device="cuda")
     def fn():
-        check(lib().tavsr_probe_seam(kind, G, C.c_int64(per_wg), NPH, C.c_void_p(addr(buf)), C.c_void_p(addr(ctl)), C.c_uint32(0), stream()), "seam")
+        check(lib().tavsr_probe_seam(kind, G, per_wg, NPH, addr(buf), addr(ctl), 0, stream()), "seam")
     s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         fn()
@@ -49,7 +49,7 @@ for shift, what in ((0, "its OWN slab of the phase before"), (8, "the slab of a 
 def chain_of(nph, per_wg, reps=100):
     buf = torch.zeros(NPH * G * per_wg, device="cuda")
     def fn():
-        check(lib().tavsr_probe_seam(0, G, C.c_int64(per_wg), nph, C.c_void_p(addr(buf)), C.c_void_p(addr(ctl)), C.c_uint32(0), stream()), "seam")
+        check(lib().tavsr_probe_seam(0, G, per_wg, nph, addr(buf), addr(ctl), 0, stream()), "seam")
     s = torch.cuda.Stream(); s.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(s):
         fn()

@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 
 import torch
 
@@ -16,168 +17,93 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # TAVSR_LIB selects another build of the same library (profiles/gemm_trace.py's instrumented one); never a fallback.
 LIB_PATH = os.environ.get("TAVSR_LIB") or os.path.join(_HERE, "lib", "libtavsr_hip.so")
 
-ACT = {None: 0, "none": 0, "relu": 1, "swish": 2, "gelu": 3, "tanh": 4, "hardtanh": 5, "selu": 6}
-
 
 class TavsrError(RuntimeError):
     pass
 
 
-class GemmDesc(C.Structure):
-    _fields_ = [
-        ("M", C.c_int32), ("N", C.c_int32), ("K", C.c_int32),
-        ("a_kmajor", C.c_int32), ("b_kmajor", C.c_int32),
-        ("A", C.c_void_p), ("lda", C.c_int64),
-        ("B", C.c_void_p), ("ldb", C.c_int64),
-        ("C", C.c_void_p), ("ldc", C.c_int64),
-        ("nb1", C.c_int32), ("nb2", C.c_int32),
-        ("sA1", C.c_int64), ("sA2", C.c_int64), ("sB1", C.c_int64), ("sB2", C.c_int64),
-        ("sC1", C.c_int64), ("sC2", C.c_int64),
-        ("bias", C.c_void_p),
-        ("act", C.c_int32), ("alpha", C.c_float),
-        ("Z", C.c_void_p),
-        ("R", C.c_void_p), ("ldr", C.c_int64), ("sR1", C.c_int64), ("sR2", C.c_int64),
-        ("DZ", C.c_void_p), ("dact", C.c_int32),
-        ("ws", C.c_void_p), ("ws_floats", C.c_int64),
-        ("a_rowsum", C.c_void_p),
-        ("conv_mode", C.c_int32), ("conv_H", C.c_int32), ("conv_W", C.c_int32), ("conv_C", C.c_int32),
-        ("conv_zero", C.c_void_p), ("conv_stride", C.c_int32), ("conv_taps", C.c_int32),
-        ("drop_p", C.c_float), ("drop_seed", C.c_void_p), ("drop_offset", C.c_uint64),
-        ("rowstat", C.c_void_p), ("rowdot_a", C.c_void_p), ("rowdot_b", C.c_void_p),
-    ]
+# ---------------------------------------------------------------------------------------------- the binding, read from the header
+# include/tavsr.h is the only declaration of the C ABI: the descriptor classes, every entry point's argtypes / restype and the
+# activation codes below are derived from it when this module is imported (no C parser: the header keeps to one regular dialect,
+# and a declaration outside it is an error, not a guess).  tests/test_binding.py checks the layouts against the C compiler's.
+HEADER_PATH = os.path.join(_HERE, "..", "..", "include", "tavsr.h")
+_SCALARS = {"int": C.c_int, "uint8_t": C.c_uint8, "int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "float": C.c_float, "double": C.c_double}
+_POINTEES = set(_SCALARS) | {"void", "char"}
+_DECL = re.compile(r"(\w+)\s*((?:\*\s*)*)(\w*)\s*(?:\[(\d+)\])?$")
 
 
-class AttnDesc(C.Structure):
-    """tavsr_attn_desc (include/tavsr.h)"""
-    _fields_ = [
-        ("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p),
-        ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64),
-        ("pos", C.c_void_p), ("ldp", C.c_int64),
-        ("bias_u", C.c_void_p), ("bias_v", C.c_void_p),
-        ("klens", C.c_void_p),
-        ("B", C.c_int32), ("H", C.c_int32), ("T1", C.c_int32), ("T2", C.c_int32), ("dk", C.c_int32),
-        ("scale", C.c_float), ("causal", C.c_int32), ("p_drop", C.c_float),
-        ("seed_dev", C.c_void_p), ("drop_offset", C.c_uint64),
-    ]
+def _class_name(struct):
+    return "".join(w.capitalize() for w in struct.split("_")[1:])
 
 
-class BfLayerDesc(C.Structure):
-    """tavsr_bf_layer_desc (include/tavsr.h): field order is the header's"""
-    _P = C.c_void_p
-    _fields_ = (
-        [(n, C.c_int32) for n in ("B", "T", "D", "H", "ffn_units", "cg_units", "cg_kernel", "ffn_act", "save")]
-        + [(n, C.c_float) for n in ("p_drop", "p_att", "coeff")]
-        + [(n, C.c_void_p) for n in (
-            "x", "pos_emb", "lens",
-            "ffm_ln_w", "ffm_ln_b", "ffm_w1", "ffm_b1", "ffm_w2", "ffm_b2",
-            "mha_ln_w", "mha_ln_b", "wq", "bq", "wk", "bk", "wv", "bv", "wpos", "pos_u", "pos_v", "wo", "bo",
-            "mlp_ln_w", "mlp_ln_b", "cg_w1", "cg_b1", "csgu_ln_w", "csgu_ln_b", "csgu_cw", "csgu_cb", "cg_w2", "cg_b2")]
-        + [("merge_p", C.c_void_p * 8)]
-        + [(n, C.c_void_p) for n in (
-            "merge_w", "merge_b", "ff_ln_w", "ff_ln_b", "ff_w1", "ff_b1", "ff_w2", "ff_b2", "final_ln_w", "final_ln_b", "seed")]
-        + [("drop_off", C.c_uint64 * 9)]
-        + [(n, C.c_void_p) for n in (
-            "x1", "ffm_n", "ffm_mean", "ffm_rstd", "ffm_z", "ffm_h",
-            "n_mha", "n_mlp", "br_mean", "br_rstd",
-            "qkv", "pp", "cx", "lse", "xa",
-            "g", "g_z", "gn", "g_mean", "g_rstd", "u", "conv", "xm",
-            "score", "pooled", "wts", "m",
-            "x2", "ff_n", "ff_mean", "ff_rstd", "ff_z", "ff_h", "x3", "y", "fin_mean", "fin_rstd",
-            "stream2", "ev_fork", "ev_join", "ws")]
-        + [("ws_floats", C.c_int64)]
-    )
+def read_header(text):
+    """(structs, prototypes, enums) of a header in the dialect of include/tavsr.h: ``typedef struct tavsr_x {...} tavsr_x;`` ->
+    {"tavsr_x": Structure class}, ``ret tavsr_f(args);`` -> {"tavsr_f": (restype, [argtypes])}, enumerators -> {name: value}.
+    Scalars map to their ctypes type, ``const char*`` to c_char_p, ``tavsr_stream_t`` and every data pointer to c_void_p; a
+    pointer to a descriptor is POINTER(struct) as a field (assigning ``C.pointer(d)`` keeps ``d`` alive) and c_void_p as an
+    argument (byref, a raw address or None).  Anything else raises TavsrError: a declaration is never skipped or guessed."""
+    structs, protos, enums = {}, {}, {}
+
+    def ctype(decl, where, field=False):
+        m = _DECL.match(re.sub(r"\bconst\b", " ", decl).strip())
+        if not m:
+            raise TavsrError(f"include/tavsr.h: cannot read `{decl.strip()}` in {where}")
+        base, stars, name, dim = m[1], m[2].count("*"), m[3], m[4]
+        if field and not name:
+            raise TavsrError(f"include/tavsr.h: field without a name `{decl.strip()}` in {where}")
+        if base == "tavsr_stream_t":
+            t = C.c_void_p
+        elif stars == 0 and base in _SCALARS:
+            t = _SCALARS[base]
+        elif stars == 1 and base == "char":
+            t = C.c_char_p
+        elif stars == 1 and base in structs:
+            t = C.POINTER(structs[base]) if field else C.c_void_p
+        elif stars >= 1 and base in _POINTEES:
+            t = C.c_void_p
+        else:
+            raise TavsrError(f"include/tavsr.h: unknown type in `{decl.strip()}` in {where}")
+        return name, t * int(dim) if dim else t
+
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)
+    text = re.sub(r'extern\s+"C"\s*\{|^\s*\}\s*$', " ", text, flags=re.M)
+    text = text.replace("typedef void* tavsr_stream_t;", " ")
+
+    def enum(m):
+        for item in m[1].split(","):
+            name, value = item.split("=")
+            enums[name.strip()] = int(value)
+        return " "
+
+    def struct(m):
+        fields = []
+        for stmt in filter(str.strip, m[2].split(";")):
+            first, *rest = stmt.split(",")          # `const float *q, *k, *v`: the later declarators repeat the first one's base type
+            fields.append(ctype(first, m[1], field=True))
+            base = re.match(r"\s*(?:const\s+)?\w+", first)[0]
+            fields += [ctype(f"{base} {d}", m[1], field=True) for d in rest]
+        structs[m[1]] = type(_class_name(m[1]), (C.Structure,), {"_fields_": fields, "__doc__": f"{m[1]} (include/tavsr.h)"})
+        return " "
+
+    text = re.sub(r"enum\s*\{([^}]*)\}\s*;", enum, text)
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^}]*)\}\s*\1\s*;", struct, text)
+    for stmt in filter(str.strip, text.split(";")):
+        m = re.match(r"\s*([\w\s\*]+?)\b(tavsr_\w+)\s*\((.*)\)\s*$", stmt, flags=re.S)
+        if not m:
+            raise TavsrError(f"include/tavsr.h: cannot read `{' '.join(stmt.split())}`")
+        args = [] if m[3].strip() == "void" else [ctype(a, m[2])[1] for a in m[3].split(",")]
+        protos[m[2]] = (ctype(m[1], m[2])[1], args)
+    return structs, protos, enums
 
 
-class BfLayerBwdDesc(C.Structure):
-    """tavsr_bf_layer_bwd_desc (include/tavsr.h)"""
-    _fields_ = (
-        [("fwd", C.POINTER(BfLayerDesc)), ("dy", C.c_void_p), ("dx", C.c_void_p)]
-        + [(n, C.c_void_p) for n in (
-            "g_ffm_w1", "g_ffm_b1", "g_ffm_w2", "g_ffm_b2",
-            "g_wq", "g_bq", "g_wk", "g_bk", "g_wv", "g_bv", "g_wo", "g_bo", "g_wpos", "g_pos_u", "g_pos_v",
-            "g_cg_w1", "g_cg_b1", "g_csgu_ln_w", "g_csgu_ln_b", "g_csgu_cw", "g_csgu_cb", "g_cg_w2", "g_cg_b2")]
-        + [("g_merge_p", C.c_void_p * 8)]
-        + [(n, C.c_void_p) for n in ("g_merge_w", "g_merge_b", "g_ff_w1", "g_ff_b1", "g_ff_w2", "g_ff_b2", "g_ln", "ws")]
-        + [("ws_floats", C.c_int64), ("wgrad_beside", C.c_int32)]
-    )
-
-
-class TailoredStreamDesc(C.Structure):
-    """tavsr_tailored_stream_desc (include/tavsr.h): field order is the header's"""
-    _fields_ = (
-        [(n, C.c_int32) for n in ("B", "T", "D", "H", "ffn_units", "cg_units", "cg_kernel", "ffn_act", "save", "use_attn")]
-        + [(n, C.c_float) for n in ("p_drop", "p_att", "coeff")]
-        + [(n, C.c_void_p) for n in (
-            "x", "pos_emb", "lens",
-            "ffm_ln_w", "ffm_ln_b", "ffm_w1", "ffm_b1", "ffm_w2", "ffm_b2", "br_ln_w", "br_ln_b",
-            "wq", "bq", "wk", "bk", "wv", "bv", "wpos", "pos_u", "pos_v", "wo", "bo",
-            "cg_w1", "cg_b1", "csgu_ln_w", "csgu_ln_b", "csgu_cw", "csgu_cb", "cg_w2", "cg_b2",
-            "ff_ln_w", "ff_ln_b", "ff_w1", "ff_b1", "ff_w2", "ff_b2", "final_ln_w", "final_ln_b", "seed")]
-        + [("drop_off", C.c_uint64 * 6)]
-        + [(n, C.c_void_p) for n in (
-            "x1", "ffm_n", "ffm_mean", "ffm_rstd", "ffm_z", "ffm_h", "n_br", "br_mean", "br_rstd",
-            "qkv", "pp", "cx", "lse", "g", "g_z", "gn", "g_mean", "g_rstd", "u", "conv",
-            "x2", "ff_n", "ff_mean", "ff_rstd", "ff_z", "ff_h", "x3", "y", "fin_mean", "fin_rstd", "ws")]
-        + [("ws_floats", C.c_int64)]
-    )
-
-
-class TailoredLayerDesc(C.Structure):
-    """tavsr_tailored_layer_desc (include/tavsr.h)"""
-    _fields_ = [("audio", C.POINTER(TailoredStreamDesc)), ("video", C.POINTER(TailoredStreamDesc)), ("stream2", C.c_void_p),
-                ("ev_fork", C.c_void_p), ("ev_join", C.c_void_p)]
-
-
-class CgmlpDesc(C.Structure):
-    """tavsr_cgmlp_desc (include/tavsr.h)"""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "T", "D", "units", "kernel", "save")]
-                + [(n, C.c_float) for n in ("p_drop", "p_out", "alpha")]
-                + [("seed", C.c_void_p), ("off_u", C.c_uint64), ("off_out", C.c_uint64)]
-                + [(n, C.c_void_p) for n in ("x", "res", "w1", "b1", "ln_w", "ln_b", "cw", "cb", "w2", "b2",
-                                             "g", "g_z", "gn", "g_mean", "g_rstd", "u", "conv", "out", "ws")]
-                + [("ws_floats", C.c_int64)])
-
-
-class CgmlpBwdDesc(C.Structure):
-    """tavsr_cgmlp_bwd_desc (include/tavsr.h)"""
-    _fields_ = ([("fwd", C.POINTER(CgmlpDesc)), ("dy", C.c_void_p), ("dx", C.c_void_p)]
-                + [(n, C.c_void_p) for n in ("g_w1", "g_b1", "g_ln_w", "g_ln_b", "g_cw", "g_cb", "g_w2", "g_b2", "ws")]
-                + [("ws_floats", C.c_int64)])
-
-
-class SubsampleDesc(C.Structure):
-    """tavsr_subsample_desc (include/tavsr.h)"""
-    _fields_ = ([(n, C.c_int32) for n in ("B", "T", "F", "C", "odim")] + [("xscale", C.c_float)]
-                + [(n, C.c_void_p) for n in ("x", "w1", "b1", "w2", "b2", "wo", "bo", "zero_page", "y1", "y2", "w2r", "wor", "out", "ws")]
-                + [("ws_floats", C.c_int64)])
-
-
-class SubsampleBwdDesc(C.Structure):
-    """tavsr_subsample_bwd_desc (include/tavsr.h)"""
-    _fields_ = ([("fwd", C.POINTER(SubsampleDesc)), ("dout", C.c_void_p)]
-                + [(n, C.c_void_p) for n in ("g_w1", "g_b1", "g_w2", "g_b2", "g_wo", "g_bo", "ws")]
-                + [("ws_floats", C.c_int64), ("wgrad_beside", C.c_int32), ("stream2", C.c_void_p), ("ev_fork", C.c_void_p)])
-
-
-class FfnDesc(C.Structure):
-    """tavsr_ffn_desc (include/tavsr.h)"""
-    _fields_ = [
-        ("M", C.c_int32), ("D", C.c_int32), ("N1", C.c_int32), ("act", C.c_int32),
-        ("scale", C.c_float), ("eps", C.c_float),
-        ("x", C.c_void_p), ("ldx", C.c_int64),
-        ("res", C.c_void_p), ("ldr", C.c_int64),
-        ("ln_w", C.c_void_p), ("ln_b", C.c_void_p), ("w1", C.c_void_p), ("b1", C.c_void_p), ("w2", C.c_void_p),
-        ("b2", C.c_void_p),
-        ("y", C.c_void_p),
-        ("p_drop", C.c_float),
-        ("seed", C.c_void_p),
-        ("offset_in", C.c_uint64), ("offset_out", C.c_uint64),
-        ("n_out", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p), ("z", C.c_void_p), ("h", C.c_void_p),
-        ("ln2_w", C.c_void_p * 2), ("ln2_b", C.c_void_p * 2), ("ln2_out", C.c_void_p * 2),
-        ("ln2_mean", C.c_void_p), ("ln2_rstd", C.c_void_p),
-        ("ln2_eps", C.c_float),
-        ("ws", C.c_void_p), ("ws_floats", C.c_int64),
-    ]
+with open(HEADER_PATH) as _f:
+    STRUCTS, PROTOTYPES, ENUMS = read_header(_f.read())
+# GemmDesc, AttnDesc, FfnDesc, BfLayerDesc, BfLayerBwdDesc, TailoredStreamDesc, TailoredLayerDesc, CgmlpDesc, CgmlpBwdDesc,
+# SubsampleDesc, SubsampleBwdDesc: tavsr_gemm_desc -> GemmDesc, ...
+globals().update({cls.__name__: cls for cls in STRUCTS.values()})
+ACT = {None: 0, **{k[len("TAVSR_ACT_"):].lower(): v for k, v in ENUMS.items() if k.startswith("TAVSR_ACT_")}}
 
 
 _lib = None
@@ -192,12 +118,12 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback for the product path.")
         _lib = C.CDLL(LIB_PATH)
-        _lib.tavsr_last_error_string.restype = C.c_char_p
-        _lib.tavsr_version.restype = C.c_int
-        _lib.tavsr_gemm_ws.restype = C.c_int64
+        for name, (restype, argtypes) in PROTOTYPES.items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, argtypes
         us = float(os.environ.get("TAVSR_RACE_PROBE", "0") or 0)
         if us > 0:      # race amplifier of the C-side sequencers (tests; ops.py arms the Python-side scopes from the same variables)
-            _lib.tavsr_race_probe(C.c_float(us), {"body": 0, "join": 1, "alt": 2}[os.environ.get("TAVSR_RACE_PROBE_MODE", "alt")])
+            _lib.tavsr_race_probe(us, {"body": 0, "join": 1, "alt": 2}[os.environ.get("TAVSR_RACE_PROBE_MODE", "alt")])
     return _lib
 
 
@@ -210,12 +136,12 @@ def check(rc: int, what: str) -> None:
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
-def stream() -> C.c_void_p:
+def stream() -> int:
     """torch's current HIP stream of the current device as a raw handle (the fast private accessor when torch has it:
     torch.cuda.current_stream() builds a Stream object per call, ~9 us, and a step makes ~1100 calls)."""
     if _raw_stream is not None:
-        return C.c_void_p(_raw_stream(torch.cuda.current_device()))
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
 
 
 # ---------------------------------------------------------------------------------------------- stream safety
@@ -295,12 +221,13 @@ def guarded(fn):
     return wrapper
 
 
-def ptr(t) -> C.c_void_p:
+def ptr(t):
+    """device address of ``t`` as a plain integer (every pointer parameter is declared c_void_p); None stays None (NULL)"""
     if t is None:
-        return C.c_void_p(0)
+        return None
     if _CUR_FORK is not None:
         _note(t)
-    return C.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
 def addr(t, off: int = 0):

@@ -54,7 +54,7 @@ def _rccl_init(rank: int, world: int, device: torch.device) -> bool:
     raw = bytes(ident.cpu().tolist())
     if not any(raw):
         raise RuntimeError("rank 0 could not create the RCCL communicator id")
-    check(lib().tavsr_dp_init(rank, world, C.c_char_p(raw)), "tavsr_dp_init")
+    check(lib().tavsr_dp_init(rank, world, raw), "tavsr_dp_init")
     return True
 
 
@@ -90,7 +90,7 @@ def _rccl_init_world1(device: torch.device) -> None:
     torch.cuda.set_device(device)
     buf = (C.c_char * 128)()
     check(lib().tavsr_dp_unique_id(buf), "tavsr_dp_unique_id")
-    check(lib().tavsr_dp_init(0, 1, C.c_char_p(buf.raw)), "tavsr_dp_init")
+    check(lib().tavsr_dp_init(0, 1, buf.raw), "tavsr_dp_init")
     RCCL_ABI = FORCE_WORLD1 = True
 
 
@@ -269,8 +269,8 @@ class GradBuckets:
             flat = torch.cat([p.data.reshape(-1) for p in bucket])
             if RCCL_ABI and flat.is_cuda:
                 from ._lib import check, lib
-                check(lib().tavsr_dp_broadcast(L_ptr(flat), C.c_int64(flat.numel()), src,
-                                               C.c_void_p(torch.cuda.current_stream().cuda_stream)), "tavsr_dp_broadcast")
+                check(lib().tavsr_dp_broadcast(L_ptr(flat), flat.numel(), src,
+                                               torch.cuda.current_stream().cuda_stream), "tavsr_dp_broadcast")
             else:
                 dist.broadcast(flat, src)
             off = 0
@@ -371,7 +371,7 @@ class GradBuckets:
         if RCCL_ABI:
             comm = self._comm_stream()
             comm.wait_stream(torch.cuda.current_stream())
-            check(lib().tavsr_dp_allreduce(L_ptr(flat), C.c_int64(flat.numel()), C.c_void_p(comm.cuda_stream)),
+            check(lib().tavsr_dp_allreduce(L_ptr(flat), flat.numel(), comm.cuda_stream),
                   "tavsr_dp_allreduce")
             self._works[i] = "rccl"
         elif dist.get_backend() == "gloo" and GLOO_HOST_STAGED:

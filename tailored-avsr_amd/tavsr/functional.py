@@ -435,12 +435,10 @@ def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
     key = (B, T, D, H, N1, C2, int(need), pd > 0.0, pa > 0.0)
     nws = _LAYER_WS.get(key)
     if nws is None:
-        fn = lib().tavsr_branchformer_layer_ws
-        fn.restype = C.c_int64
-        nws = _LAYER_WS[key] = int(fn(C.byref(d)))
+        nws = _LAYER_WS[key] = lib().tavsr_branchformer_layer_ws(C.byref(d))
     ws = ops.empty(max(nws, 4), like=x)
     d.ws, d.ws_floats = ops._addr(ws), nws
-    check(lib().tavsr_branchformer_layer_fwd(C.byref(d), C.c_void_p(main.cuda_stream)), "tavsr_branchformer_layer_fwd")
+    check(lib().tavsr_branchformer_layer_fwd(C.byref(d), main.cuda_stream), "tavsr_branchformer_layer_fwd")
     ctx.sv, ctx.cfg, ctx.P, ctx.lens, ctx.pos_emb = _LazySV(flat, off, x2d, toks, wts), cfg, P, lens, pos_emb
     ctx.shape = (B, T, D)
     if need:
@@ -535,14 +533,12 @@ def _layer_c_backward(ctx, dy):
     key = ("bwd", B, T, D, d.H, d.ffn_units, d.cg_units, d.p_drop > 0.0)
     nws = _LAYER_WS.get(key)
     if nws is None:
-        fn = lib().tavsr_branchformer_layer_bwd_ws
-        fn.restype = C.c_int64
-        nws = _LAYER_WS[key] = int(fn(C.byref(b)))
+        nws = _LAYER_WS[key] = lib().tavsr_branchformer_layer_bwd_ws(C.byref(b))
     ws = ops.empty(max(nws, 4), like=dy2)
     b.ws, b.ws_floats = ops._addr(ws), nws
     beside = side is not main and ops.WGRAD_SLOT == 0 and ops.wgrad_may_go_beside(P) and ops.wgrad_open(main, side)
     b.wgrad_beside = 1 if beside else 0
-    check(lib().tavsr_branchformer_layer_bwd(C.byref(b), C.c_void_p(main.cuda_stream)), "tavsr_branchformer_layer_bwd")
+    check(lib().tavsr_branchformer_layer_bwd(C.byref(b), main.cuda_stream), "tavsr_branchformer_layer_bwd")
     if beside:      # what those launches read and write is freed on THIS stream (rule 1 of _lib.py, by hand: the addresses were taken here)
         sv = ctx.sv
         for t in (ws, gflat, dy2, sv.flat, sv.x2d, sv.wts, ctx.pos_emb):

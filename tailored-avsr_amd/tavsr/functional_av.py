@@ -578,9 +578,7 @@ def _ts_c_desc(ns, x, pos_emb, lens, cfg, p, names, need):
     key = (B, T, D, H, N1, int(ua), d.cg_units, int(need))
     nws = _TS_WS.get(key)
     if nws is None:
-        fn = lib().tavsr_tailored_stream_ws
-        fn.restype = C.c_int64
-        nws = _TS_WS[key] = int(fn(C.byref(d)))
+        nws = _TS_WS[key] = lib().tavsr_tailored_stream_ws(C.byref(d))
     ws = ops.empty(max(nws, 4), like=x)
     d.ws, d.ws_floats = ops._addr(ws), nws
     g = b.get
@@ -608,7 +606,7 @@ def _tailored_c_forward(ca, cv, audio, apos, alens, cfg_a, video, vpos, vlens, c
     L = TailoredLayerDesc()
     L.audio, L.video = C.pointer(da), C.pointer(dv)
     L.stream2, L.ev_fork, L.ev_join = side.cuda_stream, ev[0].cuda_event, ev[1].cuda_event
-    check(lib().tavsr_tailored_layer_fwd(C.byref(L), C.c_void_p(main.cuda_stream)), "tavsr_tailored_layer_fwd")
+    check(lib().tavsr_tailored_layer_fwd(C.byref(L), main.cuda_stream), "tavsr_tailored_layer_fwd")
     return ya, yv
 
 

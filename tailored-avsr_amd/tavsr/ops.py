@@ -117,8 +117,7 @@ def gemm(M, N, K, A, lda, B, ldb, Cc, ldc, *, a_off=0, b_off=0, c_off=0, a_kmajo
         if ln is not None:
             assert force is None
             require_cuda(ln[0], ln[1], ln[3])
-            check(lib().tavsr_gemm_ln(C.byref(d), ptr(ln[0]), ptr(ln[1]), C.c_float(ln[2]), ptr(ln[3]), C.c_int64(ln[3].stride(0)),
-                                      stream()), "tavsr_gemm_ln")
+            check(lib().tavsr_gemm_ln(C.byref(d), ptr(ln[0]), ptr(ln[1]), ln[2], ptr(ln[3]), ln[3].stride(0), stream()), "tavsr_gemm_ln")
         elif force is None:
             check(lib().tavsr_gemm(C.byref(d), stream()), "tavsr_gemm")
         else:
@@ -310,14 +309,14 @@ _PROBE_TICK = [0]
 
 def spin(us: float) -> None:
     """occupies the current stream for ``us`` microseconds (one wave polling the wall clock)"""
-    check(lib().tavsr_spin(C.c_float(us), stream()), "tavsr_spin")
+    check(lib().tavsr_spin(us, stream()), "tavsr_spin")
 
 
 def arm_race_probe(us: float, mode: str = "alt") -> None:
     """(tests) set the amplifier at run time, for the Python-side scopes and the C-side sequencers alike"""
     global RACE_PROBE_US, RACE_PROBE_MODE
     RACE_PROBE_US, RACE_PROBE_MODE = float(us), mode
-    check(lib().tavsr_race_probe(C.c_float(us), {"body": 0, "join": 1, "alt": 2}[mode]), "tavsr_race_probe")
+    check(lib().tavsr_race_probe(us, {"body": 0, "join": 1, "alt": 2}[mode]), "tavsr_race_probe")
 
 
 def _probe(where: str, tick: int) -> None:
@@ -588,9 +587,8 @@ def colsum(x, *, scale=1.0, out=None, accumulate=False):
     require_cuda(x)
     if out is None:
         out = empty(N, like=x)
-    ws = empty(lib_i64("tavsr_colsum_ws", M, N), like=x)
-    check(lib().tavsr_colsum(ptr(x), C.c_int64(x.stride(0)), M, N, C.c_float(scale), ptr(out), int(accumulate), ptr(ws),
-                             stream()), "tavsr_colsum")
+    ws = empty(lib().tavsr_colsum_ws(M, N), like=x)
+    check(lib().tavsr_colsum(ptr(x), x.stride(0), M, N, scale, ptr(out), int(accumulate), ptr(ws), stream()), "tavsr_colsum")
     return out
 
 
@@ -600,23 +598,16 @@ def add2_colsum(x, y, out, lazy_sums=False):
     M, N = x.shape
     require_cuda(x, y, out)
     sx, sy = empty(N, like=x), empty(N, like=x)
-    nws = lib_i64("tavsr_colsum_ws", M, N)
+    nws = lib().tavsr_colsum_ws(M, N)
     ws = empty(2 * nws, like=x)
-    check(lib().tavsr_add2_colsum(ptr(x), C.c_int64(x.stride(0)), ptr(y), C.c_int64(y.stride(0)), ptr(out),
-                                  C.c_int64(out.stride(0)), M, N, ptr(None if lazy_sums else sx), ptr(None if lazy_sums else sy), ptr(ws),
-                                  stream()), "tavsr_add2_colsum")
+    check(lib().tavsr_add2_colsum(ptr(x), x.stride(0), ptr(y), y.stride(0), ptr(out), out.stride(0), M, N, ptr(None if lazy_sums else sx),
+                                  ptr(None if lazy_sums else sy), ptr(ws), stream()), "tavsr_add2_colsum")
     if not lazy_sums:
         return sx, sy
 
     def reduce():
-        check(lib().tavsr_sum_partials2(ptr(ws), nws // N, C.c_int64(2 * N), ptr(sx), N, ptr(sy), N, 0, stream()), "tavsr_sum_partials2")
+        check(lib().tavsr_sum_partials2(ptr(ws), nws // N, 2 * N, ptr(sx), N, ptr(sy), N, 0, stream()), "tavsr_sum_partials2")
     return sx, sy, reduce
-
-
-def lib_i64(name, *args) -> int:
-    fn = getattr(lib(), name)
-    fn.restype = C.c_int64
-    return int(fn(*args))
 
 
 # ---------------------------------------------------------------------------------------------- norms
@@ -626,8 +617,8 @@ def layernorm_fwd(x, gamma, beta, eps, *, save=True):
     y = empty(M, D, like=x)
     mean = empty(M, like=x) if save else None
     rstd = empty(M, like=x) if save else None
-    check(lib().tavsr_layernorm_fwd(ptr(x), C.c_int64(x.stride(0)), ptr(gamma), ptr(beta), C.c_float(eps), ptr(y),
-                                    C.c_int64(D), ptr(mean), ptr(rstd), M, D, stream()), "tavsr_layernorm_fwd")
+    check(lib().tavsr_layernorm_fwd(ptr(x), x.stride(0), ptr(gamma), ptr(beta), eps, ptr(y), D, ptr(mean), ptr(rstd), M, D, stream()),
+          "tavsr_layernorm_fwd")
     return y, mean, rstd
 
 
@@ -638,12 +629,10 @@ def layernorm_bwd(dy, x, mean, rstd, gamma, *, dx_add=None, dx=None):
     if dx is None:
         dx = empty(M, D, like=x)
     dg, db = empty(D, like=x), empty(D, like=x)
-    ws = empty(lib_i64("tavsr_layernorm_bwd_ws", M, D), like=x)
-    check(lib().tavsr_layernorm_bwd(ptr(dy), C.c_int64(dy.stride(0)), ptr(x), C.c_int64(x.stride(0)), ptr(mean),
-                                    ptr(rstd), ptr(gamma), ptr(dx_add),
-                                    C.c_int64(0 if dx_add is None else dx_add.stride(0)), ptr(dx),
-                                    C.c_int64(dx.stride(0)), ptr(dg), ptr(db), 0, ptr(ws), M, D, stream()),
-          "tavsr_layernorm_bwd")
+    ws = empty(lib().tavsr_layernorm_bwd_ws(M, D), like=x)
+    check(lib().tavsr_layernorm_bwd(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx_add),
+                                    0 if dx_add is None else dx_add.stride(0), ptr(dx), dx.stride(0), ptr(dg), ptr(db), 0, ptr(ws), M, D,
+                                    stream()), "tavsr_layernorm_bwd")
     return dx, dg, db
 
 
@@ -654,10 +643,10 @@ def layernorm_bwd_act(dy, x, mean, rstd, gamma, z, act, *, dx=None):
     if dx is None:
         dx = empty(M, D, like=x)
     dg, db = empty(D, like=x), empty(D, like=x)
-    ws = empty(lib_i64("tavsr_layernorm_bwd_ws", M, D), like=x)
-    check(lib().tavsr_layernorm_bwd_act(ptr(dy), C.c_int64(dy.stride(0)), ptr(x), C.c_int64(x.stride(0)), ptr(mean), ptr(rstd),
-                                        ptr(gamma), ptr(dx), C.c_int64(dx.stride(0)), ptr(dg), ptr(db), 0, ptr(ws), M, D, ptr(z),
-                                        C.c_int64(z.stride(0)), ACT[act], stream()), "tavsr_layernorm_bwd_act")
+    ws = empty(lib().tavsr_layernorm_bwd_ws(M, D), like=x)
+    check(lib().tavsr_layernorm_bwd_act(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx), dx.stride(0),
+                                        ptr(dg), ptr(db), 0, ptr(ws), M, D, ptr(z), z.stride(0), ACT[act], stream()),
+          "tavsr_layernorm_bwd_act")
     return dx, dg, db
 
 
@@ -689,7 +678,7 @@ class LNGroup:
             return r + (dropout(r[0], drop[0], token=drop)[0],)
         if self.key is None:
             self.key = (M, D)
-            self.nb = lib_i64("tavsr_layernorm_bwd_ws", M, D) // (2 * D)
+            self.nb = lib().tavsr_layernorm_bwd_ws(M, D) // (2 * D)
             self.slab = empty(self.nb, self.CAP * 2 * D, like=x)
             self.out = empty(self.CAP * 2 * D, like=x)
         if (M, D) != self.key or self.k >= self.CAP:
@@ -703,35 +692,26 @@ class LNGroup:
         if slabs is not None:
             dxd = empty(M, D, like=x) if drop is not None else None
             assert dx.is_contiguous()
-            check(lib().tavsr_layernorm_bwd_partial_slab(ptr(slabs.ws), slabs.wpb, slabs.rb, ptr(x), C.c_int64(x.stride(0)), ptr(mean),
-                                                         ptr(rstd), ptr(gamma), ptr(dx_add),
-                                                         C.c_int64(0 if dx_add is None else dx_add.stride(0)), ptr(dx),
-                                                         C.c_int64(dx.stride(0)), C.c_void_p(_addr(self.slab) + 4 * off),
-                                                         C.c_int64(self.slab.stride(0)), M, D, ptr(dxd),
-                                                         C.c_float(drop[0] if drop is not None else 0.0),
-                                                         ptr(drop[2] if drop is not None else None),
-                                                         C.c_uint64(drop[1] if drop is not None else 0), stream()),
-                  "tavsr_layernorm_bwd_partial_slab")
+            check(lib().tavsr_layernorm_bwd_partial_slab(ptr(slabs.ws), slabs.wpb, slabs.rb, ptr(x), x.stride(0), ptr(mean), ptr(rstd),
+                                                         ptr(gamma), ptr(dx_add), 0 if dx_add is None else dx_add.stride(0), ptr(dx),
+                                                         dx.stride(0), _addr(self.slab) + 4 * off, self.slab.stride(0), M, D, ptr(dxd),
+                                                         drop[0] if drop is not None else 0.0, ptr(drop[2] if drop is not None else None),
+                                                         drop[1] if drop is not None else 0, stream()), "tavsr_layernorm_bwd_partial_slab")
             self.k += 1
             r = (dx, self.out[off: off + D], self.out[off + D: off + 2 * D])
             return r if drop is None else r + (dxd,)
         if drop is not None:
             assert dx.is_contiguous()
             dxd = empty(M, D, like=x)
-            check(lib().tavsr_layernorm_bwd_partial_drop(ptr(dy), C.c_int64(dy.stride(0)), ptr(x), C.c_int64(x.stride(0)), ptr(mean),
-                                                         ptr(rstd), ptr(gamma), ptr(dx_add),
-                                                         C.c_int64(0 if dx_add is None else dx_add.stride(0)), ptr(dx),
-                                                         C.c_int64(dx.stride(0)), C.c_void_p(_addr(self.slab) + 4 * off),
-                                                         C.c_int64(self.slab.stride(0)), M, D, ptr(dxd), C.c_float(drop[0]),
-                                                         ptr(drop[2]), C.c_uint64(drop[1]), stream()),
-                  "tavsr_layernorm_bwd_partial_drop")
+            check(lib().tavsr_layernorm_bwd_partial_drop(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma),
+                                                         ptr(dx_add), 0 if dx_add is None else dx_add.stride(0), ptr(dx), dx.stride(0),
+                                                         _addr(self.slab) + 4 * off, self.slab.stride(0), M, D, ptr(dxd), drop[0],
+                                                         ptr(drop[2]), drop[1], stream()), "tavsr_layernorm_bwd_partial_drop")
             self.k += 1
             return dx, self.out[off: off + D], self.out[off + D: off + 2 * D], dxd
-        check(lib().tavsr_layernorm_bwd_partial(ptr(dy), C.c_int64(dy.stride(0)), ptr(x), C.c_int64(x.stride(0)), ptr(mean),
-                                                ptr(rstd), ptr(gamma), ptr(dx_add),
-                                                C.c_int64(0 if dx_add is None else dx_add.stride(0)), ptr(dx),
-                                                C.c_int64(dx.stride(0)), C.c_void_p(_addr(self.slab) + 4 * off),
-                                                C.c_int64(self.slab.stride(0)), M, D, stream()),
+        check(lib().tavsr_layernorm_bwd_partial(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(mean), ptr(rstd), ptr(gamma), ptr(dx_add),
+                                                0 if dx_add is None else dx_add.stride(0), ptr(dx), dx.stride(0),
+                                                _addr(self.slab) + 4 * off, self.slab.stride(0), M, D, stream()),
               "tavsr_layernorm_bwd_partial")
         self.k += 1
         return dx, self.out[off: off + D], self.out[off + D: off + 2 * D]
@@ -739,8 +719,8 @@ class LNGroup:
     def flush(self):
         if self.k:
             n = self.k * 2 * self.key[1]
-            check(lib().tavsr_sum_partials(ptr(self.slab), self.nb, C.c_int64(self.slab.stride(0)), ptr(self.out), n, 0,
-                                           stream()), "tavsr_sum_partials")
+            check(lib().tavsr_sum_partials(ptr(self.slab), self.nb, self.slab.stride(0), ptr(self.out), n, 0, stream()),
+                  "tavsr_sum_partials")
             self.k = 0
 
 
@@ -749,8 +729,7 @@ def add_head_bias(q, u, v):
     M, D = q.shape
     qu, qv = empty(M, D, like=q), empty(M, D, like=q)
     require_cuda(q, u, v)
-    check(lib().tavsr_add_head_bias(ptr(q), C.c_int64(q.stride(0)), ptr(u), ptr(v), ptr(qu), ptr(qv), C.c_int64(M), D,
-                                    stream()), "tavsr_add_head_bias")
+    check(lib().tavsr_add_head_bias(ptr(q), q.stride(0), ptr(u), ptr(v), ptr(qu), ptr(qv), M, D, stream()), "tavsr_add_head_bias")
     return qu, qv
 
 
@@ -775,13 +754,11 @@ def softmax_fwd(ac, bd, klens, scale, causal=False, T2=None, W=0, p_drop=0.0, to
         pv = torch.empty_like(ac)
         if token is None:
             token = _new_token(p_drop, ac.numel(), ac.device)
-        check(lib().tavsr_softmax_dropout_fwd(ptr(ac), ptr(bd), ptr(klens), ptr(attn), ptr(pv), H, B, T1, T2, W, C.c_int64(ld_s),
-                                              C.c_int64(ld_w), C.c_float(scale), int(causal), C.c_float(token[0]),
-                                              ptr(token[2]), C.c_uint64(token[1]), stream()),
-              "tavsr_softmax_dropout_fwd")
+        check(lib().tavsr_softmax_dropout_fwd(ptr(ac), ptr(bd), ptr(klens), ptr(attn), ptr(pv), H, B, T1, T2, W, ld_s, ld_w, scale,
+                                              int(causal), token[0], ptr(token[2]), token[1], stream()), "tavsr_softmax_dropout_fwd")
         return attn, pv, token
-    check(lib().tavsr_softmax_fwd(ptr(ac), ptr(bd), ptr(klens), ptr(attn), H, B, T1, T2, W, C.c_int64(ld_s),
-                                  C.c_int64(ld_w), C.c_float(scale), int(causal), stream()), "tavsr_softmax_fwd")
+    check(lib().tavsr_softmax_fwd(ptr(ac), ptr(bd), ptr(klens), ptr(attn), H, B, T1, T2, W, ld_s, ld_w, scale, int(causal), stream()),
+          "tavsr_softmax_fwd")
     return attn
 
 
@@ -795,12 +772,11 @@ def softmax_bwd(attn, dattn, scale, skew=False, T2=None, token=None):
     ld_w = pad4(W)
     sk = empty(H, B, T1, ld_w, like=attn) if skew else None
     if token is not None:
-        check(lib().tavsr_softmax_dropout_bwd(ptr(attn), ptr(dattn), ptr(ds), ptr(sk), H, B, T1, T2, W, C.c_int64(ld_s),
-                                              C.c_int64(ld_w), C.c_float(scale), C.c_float(token[0]), ptr(token[2]),
-                                              C.c_uint64(token[1]), stream()), "tavsr_softmax_dropout_bwd")
+        check(lib().tavsr_softmax_dropout_bwd(ptr(attn), ptr(dattn), ptr(ds), ptr(sk), H, B, T1, T2, W, ld_s, ld_w, scale, token[0],
+                                              ptr(token[2]), token[1], stream()), "tavsr_softmax_dropout_bwd")
         return ds, sk
-    check(lib().tavsr_softmax_bwd(ptr(attn), ptr(dattn), ptr(ds), ptr(sk), H, B, T1, T2, W, C.c_int64(ld_s),
-                                  C.c_int64(ld_w), C.c_float(scale), stream()), "tavsr_softmax_bwd")
+    check(lib().tavsr_softmax_bwd(ptr(attn), ptr(dattn), ptr(ds), ptr(sk), H, B, T1, T2, W, ld_s, ld_w, scale, stream()),
+          "tavsr_softmax_bwd")
     return ds, sk
 
 
@@ -834,7 +810,7 @@ def attn_fwd(q, q_off, k, k_off, v, v_off, B, T1, T2, H, dk, klens=None, causal=
     d = _attn_desc(q, q_off, k, k_off, v, v_off, B, T1, T2, H, dk, klens, causal, pos, bias_u, bias_v, tok)
     ctx = empty(B * T1, H * dk, like=q)
     lse = empty(B * H, T1, like=q)
-    check(lib().tavsr_attn_fwd(C.byref(d), ptr(ctx), C.c_int64(ctx.stride(0)), ptr(lse), stream()), "tavsr_attn_fwd")
+    check(lib().tavsr_attn_fwd(C.byref(d), ptr(ctx), ctx.stride(0), ptr(lse), stream()), "tavsr_attn_fwd")
     return ctx, lse, tok
 
 
@@ -852,11 +828,9 @@ def attn_bwd(dctx, ctx, lse, tok, q, q_off, k, k_off, v, v_off, B, T1, T2, H, dk
         ldw = pad4(2 * T1 - 1)
         sk = torch.zeros(H, B, T1, ldw, dtype=f32, device=q.device)      # the kernel writes the band of every row
         assert dqv.stride(0) == dq.stride(0)
-    check(lib().tavsr_attn_bwd(C.byref(d), ptr(dctx), ptr(ctx), C.c_int64(ctx.stride(0)), ptr(lse),
-                               C.c_void_p(_addr(dq, dq_off)), ptr(dqv), C.c_int64(dq.stride(0)),
-                               C.c_void_p(_addr(dk_buf, dk_off)), C.c_int64(dk_buf.stride(0)),
-                               C.c_void_p(_addr(dv_buf, dv_off)), C.c_int64(dv_buf.stride(0)), ptr(sk), C.c_int64(ldw),
-                               stream()), "tavsr_attn_bwd")
+    check(lib().tavsr_attn_bwd(C.byref(d), ptr(dctx), ptr(ctx), ctx.stride(0), ptr(lse), _addr(dq, dq_off), ptr(dqv), dq.stride(0),
+                               _addr(dk_buf, dk_off), dk_buf.stride(0), _addr(dv_buf, dv_off), dv_buf.stride(0), ptr(sk), ldw, stream()),
+          "tavsr_attn_bwd")
     return dqv, sk
 
 
@@ -914,7 +888,7 @@ def ffn2_fwd(x, ln_w, ln_b, eps, w1, b1, w2, b2, act, scale, p=0.0, save=True, l
         m2, r2 = empty(M, like=x), empty(M, like=x)
         d.ln2_mean, d.ln2_rstd = _addr(m2), _addr(r2)
     d.ln2_eps = ln2_eps
-    nws = lib_i64("tavsr_ffn2_ws", M, D, N1)
+    nws = lib().tavsr_ffn2_ws(M, D, N1)
     ws = empty(nws, like=x)
     d.ws, d.ws_floats = _addr(ws), nws
     check(lib().tavsr_ffn2_fwd(C.byref(d), stream()), "tavsr_ffn2_fwd")
@@ -942,12 +916,11 @@ def ffn2_bwd_dx(dyd, alpha, w1, w2, z, act, tok_in, sum_dn=True):
     assert w1.is_contiguous() and w2.is_contiguous() and z.is_contiguous() and z.shape == (M, N1)
     dz = empty((M + 127) // 128 * 128, N1, like=dyd)[:M]
     dn = empty(M, D, like=dyd) if sum_dn else None
-    nws = lib_i64("tavsr_ffn2_ws", M, D, N1)
+    nws = lib().tavsr_ffn2_ws(M, D, N1)
     ws = empty(nws, like=dyd)
-    check(lib().tavsr_ffn2_bwd_dx(ptr(dyd), C.c_int64(dyd.stride(0)), C.c_float(alpha), ptr(w1), ptr(w2), ptr(z), ACT[act], M, D,
-                                  N1, C.c_float(tok_in[0] if tok_in else 0.0), ptr(tok_in[2] if tok_in else None),
-                                  C.c_uint64(tok_in[1] if tok_in else 0), ptr(dz), ptr(dn), ptr(ws), C.c_int64(nws), stream()),
-          "tavsr_ffn2_bwd_dx")
+    check(lib().tavsr_ffn2_bwd_dx(ptr(dyd), dyd.stride(0), alpha, ptr(w1), ptr(w2), ptr(z), ACT[act], M, D, N1,
+                                  tok_in[0] if tok_in else 0.0, ptr(tok_in[2] if tok_in else None), tok_in[1] if tok_in else 0, ptr(dz),
+                                  ptr(dn), ptr(ws), nws, stream()), "tavsr_ffn2_bwd_dx")
     if sum_dn:
         return dz, dn
     lay = _SLAB_LAYOUT.get((M, N1))
@@ -986,8 +959,7 @@ def axpby(x, y=None, a=1.0, b=1.0, out=None):
         out = torch.empty_like(x)
     assert x.is_contiguous() and (y is None or y.is_contiguous()) and out.is_contiguous()
     require_cuda(x, y, out)
-    check(lib().tavsr_axpby(ptr(x), ptr(y), C.c_float(a), C.c_float(b), ptr(out), C.c_int64(x.numel()), stream()),
-          "tavsr_axpby")
+    check(lib().tavsr_axpby(ptr(x), ptr(y), a, b, ptr(out), x.numel(), stream()), "tavsr_axpby")
     return out
 
 
@@ -996,15 +968,14 @@ def scale_dev(x, s, c=1.0):
     require_cuda(x, s)
     assert x.is_contiguous()
     out = torch.empty_like(x)
-    check(lib().tavsr_scale_dev(ptr(x), ptr(s), C.c_float(c), ptr(out), C.c_int64(x.numel()), stream()), "tavsr_scale_dev")
+    check(lib().tavsr_scale_dev(ptr(x), ptr(s), c, ptr(out), x.numel(), stream()), "tavsr_scale_dev")
     return out
 
 
 def axpby2d(x, y, a, b, out):
     M, N = x.shape
     require_cuda(x, y, out)
-    check(lib().tavsr_axpby2d(ptr(x), C.c_int64(x.stride(0)), ptr(y), C.c_int64(0 if y is None else y.stride(0)),
-                              C.c_float(a), C.c_float(b), ptr(out), C.c_int64(out.stride(0)), C.c_int64(M), N, stream()),
+    check(lib().tavsr_axpby2d(ptr(x), x.stride(0), ptr(y), 0 if y is None else y.stride(0), a, b, ptr(out), out.stride(0), M, N, stream()),
           "tavsr_axpby2d")
     return out
 
@@ -1012,7 +983,7 @@ def axpby2d(x, y, a, b, out):
 def act_bwd_(dh, z, act):
     """in place: dh *= act'(z)."""
     assert dh.is_contiguous() and z.is_contiguous()
-    check(lib().tavsr_act_bwd(ptr(dh), ptr(z), ptr(dh), C.c_int64(dh.numel()), ACT[act], stream()), "tavsr_act_bwd")
+    check(lib().tavsr_act_bwd(ptr(dh), ptr(z), ptr(dh), dh.numel(), ACT[act], stream()), "tavsr_act_bwd")
     return dh
 
 
@@ -1022,8 +993,8 @@ def dwconv_gate_fwd(gn, r, w, bias, B, T):
     K = w.shape[-1]
     out, conv = empty(M, Cn, like=gn), empty(M, Cn, like=gn)
     require_cuda(gn, r, w, bias)
-    check(lib().tavsr_dwconv_gate_fwd(ptr(gn), ptr(r), C.c_int64(r.stride(0)), ptr(w), ptr(bias), ptr(out), ptr(conv),
-                                      B, T, Cn, K, stream()), "tavsr_dwconv_gate_fwd")
+    check(lib().tavsr_dwconv_gate_fwd(ptr(gn), ptr(r), r.stride(0), ptr(w), ptr(bias), ptr(out), ptr(conv), B, T, Cn, K, stream()),
+          "tavsr_dwconv_gate_fwd")
     return out, conv
 
 
@@ -1054,11 +1025,9 @@ def csgu_fwd(g, ln_w, ln_b, eps, w, bias, B, T, p=0.0, save=True, rowstat=None):
     conv, gn = (empty(M, Cn, like=g), empty(M, Cn, like=g)) if save else (None, None)
     mean, rstd = empty(M, like=g), empty(M, like=g)
     tok = _new_token(p, M * Cn, g.device) if p and p > 0.0 else None
-    check(lib().tavsr_csgu_fwd(ptr(g), C.c_int64(g.stride(0)), ptr(ln_w), ptr(ln_b), C.c_float(eps), ptr(w), ptr(bias), ptr(out),
-                               ptr(gn), ptr(conv), ptr(mean), ptr(rstd), C.c_float(tok[0] if tok else 0.0),
-                               ptr(tok[2] if tok else None), C.c_uint64(tok[1] if tok else 0), B, T, Cn, w.shape[-1], ptr(rowstat),
-                               stream()),
-          "tavsr_csgu_fwd")
+    check(lib().tavsr_csgu_fwd(ptr(g), g.stride(0), ptr(ln_w), ptr(ln_b), eps, ptr(w), ptr(bias), ptr(out), ptr(gn), ptr(conv), ptr(mean),
+                               ptr(rstd), tok[0] if tok else 0.0, ptr(tok[2] if tok else None), tok[1] if tok else 0, B, T, Cn, w.shape[-1],
+                               ptr(rowstat), stream()), "tavsr_csgu_fwd")
     return out, conv, gn, mean, rstd, tok
 
 
@@ -1094,7 +1063,7 @@ def cgmlp_fwd(x, w1, b1, ln_w, ln_b, cw, cb, w2, b2, B, T, *, p=0.0, p_out=0.0, 
     for f, t in (("x", x), ("res", res), ("w1", w1), ("b1", b1), ("ln_w", ln_w), ("ln_b", ln_b), ("cw", cw), ("cb", cb), ("w2", w2),
                  ("b2", b2), ("g", g), ("g_z", z), ("gn", gn), ("g_mean", gmean), ("g_rstd", grstd), ("u", u), ("conv", conv), ("out", out)):
         setattr(d, f, _addr(t))
-    nws = lib_i64("tavsr_cgmlp_ws", C.byref(d))
+    nws = lib().tavsr_cgmlp_ws(C.byref(d))
     ws = empty(max(nws, 4), like=x)
     d.ws, d.ws_floats = _addr(ws), nws
     check(lib().tavsr_cgmlp_fwd(C.byref(d), stream()), "tavsr_cgmlp_fwd")
@@ -1113,7 +1082,7 @@ def cgmlp_bwd(desc, dy, params):
     b.dy, b.dx = _addr(dy), _addr(dx)
     for f, t in zip(("g_w1", "g_b1", "g_ln_w", "g_ln_b", "g_cw", "g_cb", "g_w2", "g_b2"), grads):
         setattr(b, f, _addr(t))
-    nws = lib_i64("tavsr_cgmlp_bwd_ws", C.byref(b))
+    nws = lib().tavsr_cgmlp_bwd_ws(C.byref(b))
     ws = empty(max(nws, 4), like=dy)
     b.ws, b.ws_floats = _addr(ws), nws
     check(lib().tavsr_cgmlp_bwd(C.byref(b), stream()), "tavsr_cgmlp_bwd")
@@ -1144,7 +1113,7 @@ def conv2d_subsample_fwd(x, w1, b1, w2, b2, wo, bo, xscale):
     for f, t in (("x", x), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2), ("wo", wo), ("bo", bo), ("zero_page", _zero_page(x.device)),
                  ("y1", y1), ("y2", y2), ("w2r", w2r), ("wor", wor), ("out", out)):
         setattr(d, f, _addr(t))
-    nws = lib_i64("tavsr_conv2d_subsample_ws", C.byref(d))
+    nws = lib().tavsr_conv2d_subsample_ws(C.byref(d))
     ws = empty(max(nws, 4), like=x)
     d.ws, d.ws_floats = _addr(ws), nws
     check(lib().tavsr_conv2d_subsample_fwd(C.byref(d), stream()), "tavsr_conv2d_subsample_fwd")
@@ -1163,7 +1132,7 @@ def conv2d_subsample_bwd(desc, dout, shapes, params=None, kept=()):
     b.dout = _addr(dout)
     for f, t in zip(("g_w1", "g_b1", "g_w2", "g_b2", "g_wo", "g_bo"), grads):
         setattr(b, f, _addr(t))
-    nws = lib_i64("tavsr_conv2d_subsample_bwd_ws", C.byref(b))
+    nws = lib().tavsr_conv2d_subsample_bwd_ws(C.byref(b))
     ws = empty(max(nws, 4), like=dout)
     b.ws, b.ws_floats = _addr(ws), nws
     main = torch.cuda.current_stream()
@@ -1185,16 +1154,15 @@ def dwconv_gate_bwd(du, gn, r, conv, w, dr, B, T, zr=None, act="gelu"):
     K = w.shape[-1]
     dgn = empty(M, Cn, like=gn)
     dw, db = torch.empty_like(w), empty(Cn, like=gn)
-    ws = empty(lib_i64("tavsr_dwconv_gate_bwd_ws", B, T, Cn, K), like=gn)
+    ws = empty(lib().tavsr_dwconv_gate_bwd_ws(B, T, Cn, K), like=gn)
     if zr is not None:
         require_cuda(du, gn, r, conv, w, dr, zr)
-        check(lib().tavsr_dwconv_gate_bwd_act(ptr(du), ptr(gn), ptr(r), C.c_int64(r.stride(0)), ptr(conv), ptr(w), ptr(dr),
-                                              C.c_int64(dr.stride(0)), ptr(dgn), ptr(dw), ptr(db), 0, ptr(ws), B, T, Cn, K,
-                                              ptr(zr), C.c_int64(zr.stride(0)), ACT[act], stream()), "tavsr_dwconv_gate_bwd_act")
+        check(lib().tavsr_dwconv_gate_bwd_act(ptr(du), ptr(gn), ptr(r), r.stride(0), ptr(conv), ptr(w), ptr(dr), dr.stride(0), ptr(dgn),
+                                              ptr(dw), ptr(db), 0, ptr(ws), B, T, Cn, K, ptr(zr), zr.stride(0), ACT[act], stream()),
+              "tavsr_dwconv_gate_bwd_act")
         return dgn, dw, db
-    check(lib().tavsr_dwconv_gate_bwd(ptr(du), ptr(gn), ptr(r), C.c_int64(r.stride(0)), ptr(conv), ptr(w), ptr(dr),
-                                      C.c_int64(dr.stride(0)), ptr(dgn), ptr(dw), ptr(db), 0, ptr(ws), B, T, Cn, K,
-                                      stream()), "tavsr_dwconv_gate_bwd")
+    check(lib().tavsr_dwconv_gate_bwd(ptr(du), ptr(gn), ptr(r), r.stride(0), ptr(conv), ptr(w), ptr(dr), dr.stride(0), ptr(dgn), ptr(dw),
+                                      ptr(db), 0, ptr(ws), B, T, Cn, K, stream()), "tavsr_dwconv_gate_bwd")
     return dgn, dw, db
 
 
@@ -1259,10 +1227,10 @@ def merge_proj_fwd(x1, x2, lens, params, w, b, res, alpha, p, B, T, lens2=None, 
     tok = _new_token(p, M * D, x1.device) if p and p > 0.0 else None
     rd1, rd2 = rowdots if rowdots is not None else (None, None)      # the producers' GEMM epilogues left the row dots (linear_drop(rowdot=))
     assert rd1 is None or (rd1.shape == (M, 4, 2) and rd2.shape == (M, 4, 2) and rd1.is_contiguous() and rd2.is_contiguous())
-    check(lib().tavsr_merge_proj_fwd_dots(ptr(x1), ptr(x2), ptr(lens), ptr(lens2), _ptr_array(params), ptr(w), ptr(b), ptr(res),
-                                          C.c_float(alpha), C.c_float(p if tok is not None else 0.0), ptr(None if tok is None else tok[2]),
-                                          C.c_uint64(0 if tok is None else tok[1]), ptr(rd1), ptr(rd2), ptr(dots), ptr(score), ptr(wts),
-                                          ptr(mix), ptr(out), B, T, D, stream()), "tavsr_merge_proj_fwd_dots")
+    check(lib().tavsr_merge_proj_fwd_dots(ptr(x1), ptr(x2), ptr(lens), ptr(lens2), _ptr_array(params), ptr(w), ptr(b), ptr(res), alpha,
+                                          p if tok is not None else 0.0, ptr(None if tok is None else tok[2]), 0 if tok is None else tok[1],
+                                          ptr(rd1), ptr(rd2), ptr(dots), ptr(score), ptr(wts), ptr(mix), ptr(out), B, T, D, stream()),
+          "tavsr_merge_proj_fwd_dots")
     return score, dots, wts, mix, out, tok
 
 
@@ -1284,20 +1252,19 @@ def merge_bwd(dm, x1, x2, lens, params, score, pooled, w, B, T, lens2=None, drop
     if pooled.dim() == 2:          # row dots: the row-parallel launches
         require_cuda(dm, x1, x2, lens, lens2, score, pooled, w)
         assert dm.is_contiguous() and x1.is_contiguous() and x2.is_contiguous()
-        ws = empty(lib_i64("tavsr_merge_rows_bwd_ws", B, T, D), like=x1)
+        ws = empty(lib().tavsr_merge_rows_bwd_ws(B, T, D), like=x1)
         seed = (drop1 or drop2 or (0.0, 0, None))[2]
         assert drop1 is None or drop2 is None or drop1[2] is drop2[2] or drop1[2].data_ptr() == drop2[2].data_ptr()
         p1, o1 = (drop1[0], drop1[1]) if drop1 is not None else (0.0, 0)
         p2, o2 = (drop2[0], drop2[1]) if drop2 is not None else (0.0, 0)
         check(lib().tavsr_merge_rows_bwd(ptr(dm), ptr(x1), ptr(x2), ptr(lens), ptr(lens2), _ptr_array(params), ptr(score), ptr(w),
-                                         ptr(pooled), ptr(dx1), ptr(dx2), _ptr_array(dparams), 0, ptr(ws), C.c_float(p1),
-                                         C.c_uint64(o1), C.c_float(p2), C.c_uint64(o2), ptr(seed), B, T, D, stream()),
-              "tavsr_merge_rows_bwd")
+                                         ptr(pooled), ptr(dx1), ptr(dx2), _ptr_array(dparams), 0, ptr(ws), p1, o1, p2, o2, ptr(seed), B, T,
+                                         D, stream()), "tavsr_merge_rows_bwd")
         grads = [None] * 8
         for g, i in zip(dparams, order):
             grads[i] = g
         return dx1, dx2, grads
-    ws = empty(lib_i64("tavsr_merge_bwd_ws", B, D), like=x1)
+    ws = empty(lib().tavsr_merge_bwd_ws(B, D), like=x1)
     check(lib().tavsr_merge_bwd(ptr(dm), ptr(x1), ptr(x2), ptr(lens), ptr(lens2), _ptr_array(params), ptr(score), ptr(pooled),
                                 ptr(w), ptr(dx1), ptr(dx2), _ptr_array(dparams), 0, ptr(ws), B, T, D, stream()),
           "tavsr_merge_bwd")
@@ -1325,7 +1292,7 @@ def conv1_fwd(x, w, bias):
 def conv1_bwd(dz, x, Cn):
     B, T, F = x.shape
     dw, db = empty(Cn, 9, like=x), empty(Cn, like=x)
-    ws = empty(lib_i64("tavsr_conv1_bwd_ws", B, T, F, Cn), like=x)
+    ws = empty(lib().tavsr_conv1_bwd_ws(B, T, F, Cn), like=x)
     check(lib().tavsr_conv1_bwd(ptr(dz), ptr(x), ptr(dw), ptr(db), 0, ptr(ws), B, T, F, Cn, stream()), "tavsr_conv1_bwd")
     return dw, db
 
@@ -1350,7 +1317,7 @@ def transpose_inner(x, nb, R, Cc, out=None):
     require_cuda(x)
     if out is None:
         out = torch.empty_like(x)
-    check(lib().tavsr_transpose_inner(ptr(x), ptr(out), C.c_int64(nb), R, Cc, 0, stream()), "tavsr_transpose_inner")
+    check(lib().tavsr_transpose_inner(ptr(x), ptr(out), nb, R, Cc, 0, stream()), "tavsr_transpose_inner")
     return out
 
 
@@ -1369,10 +1336,9 @@ def ctc_loss(logits, hlens, targets, tlens, blank=0, zero_infinity=True):
     Lmax = targets.shape[1]
     require_cuda(logits, hlens, targets, tlens)
     loss, grad = empty(B, like=logits), torch.empty_like(logits)
-    ws = empty(lib_i64("tavsr_ctc_loss_ws", B, T, Lmax), like=logits)
-    check(lib().tavsr_ctc_loss(ptr(logits), C.c_int64(V), C.c_int64(T * V), ptr(hlens), ptr(targets),
-                               C.c_int64(targets.stride(0)), ptr(tlens), blank, int(zero_infinity), ptr(loss), ptr(grad),
-                               ptr(ws), B, T, V, Lmax, stream()), "tavsr_ctc_loss")
+    ws = empty(lib().tavsr_ctc_loss_ws(B, T, Lmax), like=logits)
+    check(lib().tavsr_ctc_loss(ptr(logits), V, T * V, ptr(hlens), ptr(targets), targets.stride(0), ptr(tlens), blank, int(zero_infinity),
+                               ptr(loss), ptr(grad), ptr(ws), B, T, V, Lmax, stream()), "tavsr_ctc_loss")
     return loss, grad
 
 
@@ -1382,8 +1348,8 @@ def ctc_greedy(logits, hlens=None, blank=0, collapse=True):
     ids = torch.empty((B, T), dtype=torch.int64, device=logits.device)
     hyp = torch.empty((B, T), dtype=torch.int64, device=logits.device) if collapse else None
     hl = torch.empty((B,), dtype=torch.int64, device=logits.device) if collapse else None
-    check(lib().tavsr_ctc_greedy(ptr(logits), C.c_int64(V), C.c_int64(T * V), ptr(hlens), blank, ptr(ids), ptr(hyp),
-                                 ptr(hl), B, T, V, stream()), "tavsr_ctc_greedy")
+    check(lib().tavsr_ctc_greedy(ptr(logits), V, T * V, ptr(hlens), blank, ptr(ids), ptr(hyp), ptr(hl), B, T, V, stream()),
+          "tavsr_ctc_greedy")
     return ids, hyp, hl
 
 
@@ -1399,9 +1365,9 @@ def maskctc_init(logits, hlens, blank, mask_token, threshold, n_iterations):
     tok_prob = empty(B, Lc, like=logits)
     y_len = torch.empty((B,), dtype=torch.int64, device=logits.device)
     plan = torch.empty((B, 3), dtype=torch.int32, device=logits.device)
-    check(lib().tavsr_maskctc_init(ptr(logits), C.c_int64(V), C.c_int64(T * V), ptr(hlens), int(blank), int(mask_token),
-                                   C.c_double(float(threshold)), int(n_iterations), ptr(y_in), ptr(y_hat), ptr(tok_prob),
-                                   C.c_int64(Lc), ptr(y_len), ptr(plan), B, T, V, stream()), "tavsr_maskctc_init")
+    check(lib().tavsr_maskctc_init(ptr(logits), V, T * V, ptr(hlens), int(blank), int(mask_token), float(threshold), int(n_iterations),
+                                   ptr(y_in), ptr(y_hat), ptr(tok_prob), Lc, ptr(y_len), ptr(plan), B, T, V, stream()),
+          "tavsr_maskctc_init")
     return y_in, y_hat, tok_prob, y_len, plan
 
 
@@ -1411,8 +1377,8 @@ def maskctc_step(logits, y_in, y_len, plan, it, mask_token):
     require_cuda(logits, y_in, y_len, plan)
     assert logits.is_contiguous() and logits.dtype == torch.float32 and y_in.dtype == torch.int64 and y_in.stride(1) == 1
     assert y_len.dtype == torch.int64 and plan.dtype == torch.int32 and plan.is_contiguous() and y_in.shape[1] >= L
-    check(lib().tavsr_maskctc_step(ptr(logits), C.c_int64(V1), C.c_int64(L * V1), ptr(y_in), C.c_int64(y_in.stride(0)),
-                                   ptr(y_len), ptr(plan), int(it), int(mask_token), B, L, V1, stream()), "tavsr_maskctc_step")
+    check(lib().tavsr_maskctc_step(ptr(logits), V1, L * V1, ptr(y_in), y_in.stride(0), ptr(y_len), ptr(plan), int(it), int(mask_token), B,
+                                   L, V1, stream()), "tavsr_maskctc_step")
     return y_in
 
 
@@ -1421,8 +1387,8 @@ def lsm_loss(logits2d, target, ignore, smoothing):
     require_cuda(logits2d, target)
     row_loss, grad = empty(rows, like=logits2d), torch.empty_like(logits2d)
     correct = torch.empty((rows,), dtype=torch.int32, device=logits2d.device)
-    check(lib().tavsr_lsm_loss(ptr(logits2d), C.c_int64(V), ptr(target), ignore, C.c_float(smoothing), ptr(row_loss),
-                               ptr(grad), ptr(correct), C.c_int64(rows), V, stream()), "tavsr_lsm_loss")
+    check(lib().tavsr_lsm_loss(ptr(logits2d), V, ptr(target), ignore, smoothing, ptr(row_loss), ptr(grad), ptr(correct), rows, V, stream()),
+          "tavsr_lsm_loss")
     return row_loss, grad, correct
 
 
@@ -1434,19 +1400,17 @@ def embed_pe(ids, table, pe, scale, step_dev=None):
     out = empty(B, Lq, D, like=table)
     if step_dev is not None:
         assert Lq == 1 and step_dev.dtype == torch.int32 and pe.is_contiguous() and pe.shape[1] == D
-        check(lib().tavsr_embed_pe_step(ptr(ids), ptr(table), ptr(pe), C.c_float(scale), ptr(out), C.c_int64(B), pe.shape[0], D,
-                                        ptr(step_dev), stream()), "tavsr_embed_pe_step")
+        check(lib().tavsr_embed_pe_step(ptr(ids), ptr(table), ptr(pe), scale, ptr(out), B, pe.shape[0], D, ptr(step_dev), stream()),
+              "tavsr_embed_pe_step")
         return out
-    check(lib().tavsr_embed_pe(ptr(ids), ptr(table), ptr(pe), C.c_float(scale), ptr(out), C.c_int64(B * Lq), Lq, D,
-                               stream()), "tavsr_embed_pe")
+    check(lib().tavsr_embed_pe(ptr(ids), ptr(table), ptr(pe), scale, ptr(out), B * Lq, Lq, D, stream()), "tavsr_embed_pe")
     return out
 
 
 def embed_bwd(ids, dout, scale, V):
     D = dout.shape[-1]
     dt = empty(V, D, like=dout)
-    check(lib().tavsr_embed_bwd(ptr(ids), ptr(dout), C.c_float(scale), ptr(dt), C.c_int64(ids.numel()), V, D, 0,
-                                stream()), "tavsr_embed_bwd")
+    check(lib().tavsr_embed_bwd(ptr(ids), ptr(dout), scale, ptr(dt), ids.numel(), V, D, 0, stream()), "tavsr_embed_bwd")
     return dt
 
 
@@ -1460,7 +1424,7 @@ def im2col2d(x, N, H, W, Cn, KH, KW, stride, pad):
     require_cuda(x)
     Ho, Wo = conv_out(H, KH, stride, pad), conv_out(W, KW, stride, pad)
     col = empty(N * Ho * Wo, KH * KW * Cn, like=x)
-    check(lib().tavsr_im2col2d(ptr(x), ptr(col), C.c_int64(N), H, W, Cn, KH, KW, stride, pad, stream()), "tavsr_im2col2d")
+    check(lib().tavsr_im2col2d(ptr(x), ptr(col), N, H, W, Cn, KH, KW, stride, pad, stream()), "tavsr_im2col2d")
     return col, Ho, Wo
 
 
@@ -1470,8 +1434,7 @@ def col2im2d(dcol, N, H, W, Cn, KH, KW, stride, pad, extra=None):
     require_cuda(dcol, extra)
     assert extra is None or (extra.is_contiguous() and extra.shape == (dcol.shape[0], Cn))
     dx = empty(N * H * W, Cn, like=dcol)
-    check(lib().tavsr_col2im2d(ptr(dcol), ptr(dx), C.c_int64(N), H, W, Cn, KH, KW, stride, pad, ptr(extra), stream()),
-          "tavsr_col2im2d")
+    check(lib().tavsr_col2im2d(ptr(dcol), ptr(dx), N, H, W, Cn, KH, KW, stride, pad, ptr(extra), stream()), "tavsr_col2im2d")
     return dx
 
 
@@ -1566,15 +1529,15 @@ def bn_stats(x, eps, momentum, running_mean=None, running_var=None, nbt=None):
     M, Cn = x.shape
     require_cuda(x, running_mean, running_var, nbt)
     mean, var, rstd = empty(Cn, like=x), empty(Cn, like=x), empty(Cn, like=x)
-    ws = empty(lib_i64("tavsr_bn_ws", C.c_int64(M), Cn), like=x)
-    check(lib().tavsr_bn_stats(ptr(x), C.c_int64(M), Cn, C.c_float(eps), C.c_float(momentum), ptr(mean), ptr(var), ptr(rstd),
-                               ptr(running_mean), ptr(running_var), ptr(nbt), ptr(ws), stream()), "tavsr_bn_stats")
+    ws = empty(lib().tavsr_bn_ws(M, Cn), like=x)
+    check(lib().tavsr_bn_stats(ptr(x), M, Cn, eps, momentum, ptr(mean), ptr(var), ptr(rstd), ptr(running_mean), ptr(running_var), ptr(nbt),
+                               ptr(ws), stream()), "tavsr_bn_stats")
     return mean, rstd
 
 
 def rsqrt_eps(v, eps):
     out = torch.empty_like(v)
-    check(lib().tavsr_rsqrt_eps(ptr(v), C.c_float(eps), ptr(out), C.c_int64(v.numel()), stream()), "tavsr_rsqrt_eps")
+    check(lib().tavsr_rsqrt_eps(ptr(v), eps, ptr(out), v.numel(), stream()), "tavsr_rsqrt_eps")
     return out
 
 
@@ -1582,8 +1545,8 @@ def bn_apply_fwd(x, mean, rstd, gamma, beta, res=None, act=None):
     M, Cn = x.shape
     require_cuda(x, mean, rstd, gamma, beta, res)
     y = torch.empty_like(x)
-    check(lib().tavsr_bn_apply_fwd(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(res), ptr(y), C.c_int64(M), Cn,
-                                   ACT[act], stream()), "tavsr_bn_apply_fwd")
+    check(lib().tavsr_bn_apply_fwd(ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(res), ptr(y), M, Cn, ACT[act], stream()),
+          "tavsr_bn_apply_fwd")
     return y
 
 
@@ -1595,9 +1558,9 @@ def bn_bwd(dy, x, mean, rstd, gamma, beta, res=None, act=None, need_dz=True):
     assert need_dz or res is None
     dz, dx = (torch.empty_like(x) if need_dz else None), torch.empty_like(x)
     dg, db = empty(Cn, like=x), empty(Cn, like=x)
-    ws = empty(lib_i64("tavsr_bn_ws", C.c_int64(M), Cn), like=x)
-    check(lib().tavsr_bn_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(res), ptr(dz), ptr(dx), ptr(dg),
-                             ptr(db), C.c_int64(M), Cn, ACT[act], ptr(ws), stream()), "tavsr_bn_bwd")
+    ws = empty(lib().tavsr_bn_ws(M, Cn), like=x)
+    check(lib().tavsr_bn_bwd(ptr(dy), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(res), ptr(dz), ptr(dx), ptr(dg), ptr(db), M,
+                             Cn, ACT[act], ptr(ws), stream()), "tavsr_bn_bwd")
     return dz, dx, dg, db
 
 
@@ -1608,9 +1571,9 @@ def bn_bwd_pooled(dpool, idx, x, mean, rstd, gamma, beta, N, H, W, act=None):
     assert M == N * H * W and dpool.is_contiguous() and idx.dtype == torch.uint8 and idx.is_contiguous()
     dx = torch.empty_like(x)
     dg, db = empty(Cn, like=x), empty(Cn, like=x)
-    ws = empty(lib_i64("tavsr_bn_ws", C.c_int64(M), Cn), like=x)
-    check(lib().tavsr_bn_bwd_pooled(ptr(dpool), ptr(idx), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), ptr(dg),
-                                    ptr(db), C.c_int64(N), H, W, Cn, ACT[act], ptr(ws), stream()), "tavsr_bn_bwd_pooled")
+    ws = empty(lib().tavsr_bn_ws(M, Cn), like=x)
+    check(lib().tavsr_bn_bwd_pooled(ptr(dpool), ptr(idx), ptr(x), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ptr(dx), ptr(dg), ptr(db), N,
+                                    H, W, Cn, ACT[act], ptr(ws), stream()), "tavsr_bn_bwd_pooled")
     return dx, dg, db
 
 
@@ -1618,7 +1581,7 @@ def maxpool3x3s2_fwd(x, N, H, W, Cn):
     Ho, Wo = conv_out(H, 3, 2, 1), conv_out(W, 3, 2, 1)
     y = empty(N * Ho * Wo, Cn, like=x)
     idx = torch.empty((N * Ho * Wo, Cn), dtype=torch.uint8, device=x.device)
-    check(lib().tavsr_maxpool3x3s2_fwd(ptr(x), ptr(y), ptr(idx), C.c_int64(N), H, W, Cn, stream()), "tavsr_maxpool3x3s2_fwd")
+    check(lib().tavsr_maxpool3x3s2_fwd(ptr(x), ptr(y), ptr(idx), N, H, W, Cn, stream()), "tavsr_maxpool3x3s2_fwd")
     return y, idx, Ho, Wo
 
 
@@ -1628,26 +1591,26 @@ def bn_act_maxpool3x3s2_fwd(z, mean, rstd, gamma, beta, act, N, H, W, Cn):
     require_cuda(z, mean, rstd, gamma, beta)
     y = empty(N * Ho * Wo, Cn, like=z)
     idx = torch.empty((N * Ho * Wo, Cn), dtype=torch.uint8, device=z.device)
-    check(lib().tavsr_bn_act_maxpool3x3s2_fwd(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ACT[act], ptr(y), ptr(idx),
-                                              C.c_int64(N), H, W, Cn, stream()), "tavsr_bn_act_maxpool3x3s2_fwd")
+    check(lib().tavsr_bn_act_maxpool3x3s2_fwd(ptr(z), ptr(mean), ptr(rstd), ptr(gamma), ptr(beta), ACT[act], ptr(y), ptr(idx), N, H, W, Cn,
+                                              stream()), "tavsr_bn_act_maxpool3x3s2_fwd")
     return y, idx, Ho, Wo
 
 
 def maxpool3x3s2_bwd(dy, idx, N, H, W, Cn):
     dx = empty(N * H * W, Cn, like=dy)
-    check(lib().tavsr_maxpool3x3s2_bwd(ptr(dy), ptr(idx), ptr(dx), C.c_int64(N), H, W, Cn, stream()), "tavsr_maxpool3x3s2_bwd")
+    check(lib().tavsr_maxpool3x3s2_bwd(ptr(dy), ptr(idx), ptr(dx), N, H, W, Cn, stream()), "tavsr_maxpool3x3s2_bwd")
     return dx
 
 
 def avgpool_fwd(x, N, P, Cn):
     y = empty(N, Cn, like=x)
-    check(lib().tavsr_avgpool_fwd(ptr(x), ptr(y), C.c_int64(N), P, Cn, stream()), "tavsr_avgpool_fwd")
+    check(lib().tavsr_avgpool_fwd(ptr(x), ptr(y), N, P, Cn, stream()), "tavsr_avgpool_fwd")
     return y
 
 
 def avgpool_bwd(dy, N, P, Cn):
     dx = empty(N * P, Cn, like=dy)
-    check(lib().tavsr_avgpool_bwd(ptr(dy), ptr(dx), C.c_int64(N), P, Cn, stream()), "tavsr_avgpool_bwd")
+    check(lib().tavsr_avgpool_bwd(ptr(dy), ptr(dx), N, P, Cn, stream()), "tavsr_avgpool_bwd")
     return dx
 
 
@@ -1699,7 +1662,7 @@ def conv3x3_dw(dz, x, H, W, stride=1, taps=9, pad0=False, bias_grad=False):
 def fill_(t, value):
     require_cuda(t)
     assert t.is_contiguous()
-    check(lib().tavsr_fill(ptr(t), C.c_float(value), C.c_int64(t.numel()), stream()), "tavsr_fill")
+    check(lib().tavsr_fill(ptr(t), value, t.numel(), stream()), "tavsr_fill")
     return t
 
 
@@ -1707,8 +1670,7 @@ def copy2d(src, dst):
     """dst[m, :N] = src[m, :N] for 2-D (row-strided) views of equal shape; no alignment requirement."""
     require_cuda(src, dst)
     assert src.shape == dst.shape and src.dim() == 2 and src.stride(1) == 1 and dst.stride(1) == 1
-    check(lib().tavsr_copy2d(ptr(src), C.c_int64(src.stride(0)), ptr(dst), C.c_int64(dst.stride(0)), C.c_int64(src.shape[0]),
-                             C.c_int64(src.shape[1]), stream()), "tavsr_copy2d")
+    check(lib().tavsr_copy2d(ptr(src), src.stride(0), ptr(dst), dst.stride(0), src.shape[0], src.shape[1], stream()), "tavsr_copy2d")
     return dst
 
 
@@ -1718,8 +1680,7 @@ def stft_frames(wav, window, T, n_fft, hop, center=True):
     B, N = wav.shape
     require_cuda(wav, window)
     frames = empty(B * T, n_fft, like=wav)
-    check(lib().tavsr_stft_frames(ptr(wav), ptr(window), ptr(frames), B, C.c_int64(N), T, n_fft, hop, int(center), stream()),
-          "tavsr_stft_frames")
+    check(lib().tavsr_stft_frames(ptr(wav), ptr(window), ptr(frames), B, N, T, n_fft, hop, int(center), stream()), "tavsr_stft_frames")
     return frames
 
 
@@ -1727,15 +1688,14 @@ def power_spec(spec, nfreq, ldp, B, T, olens):
     """spec [B*T, >= 2*nfreq] (re | im) -> power [B*T, ldp] (zero K padding, zero past olens)."""
     require_cuda(spec, olens)
     P = empty(B * T, ldp, like=spec)
-    check(lib().tavsr_power_spec(ptr(spec), C.c_int64(spec.stride(0)), ptr(P), ldp, nfreq, B, T, ptr(olens), stream()),
-          "tavsr_power_spec")
+    check(lib().tavsr_power_spec(ptr(spec), spec.stride(0), ptr(P), ldp, nfreq, B, T, ptr(olens), stream()), "tavsr_power_spec")
     return P
 
 
 def log_mask(mel, B, T, olens, floor=1e-10):
     require_cuda(mel, olens)
     out = torch.empty_like(mel)
-    check(lib().tavsr_log_mask(ptr(mel), ptr(out), B, T, mel.shape[-1], ptr(olens), C.c_float(floor), stream()), "tavsr_log_mask")
+    check(lib().tavsr_log_mask(ptr(mel), ptr(out), B, T, mel.shape[-1], ptr(olens), floor, stream()), "tavsr_log_mask")
     return out
 
 
@@ -1764,8 +1724,8 @@ def specaug_mask_(x, fpos=None, flen=None, tpos=None, tlen=None):
 def bucket_copy(ptrs, offs, sizes, n, flat, scale, to_flat, max_n):
     """pack (to_flat) or unpack-and-scale the tensors listed in the device tables into / from ``flat`` (tavsr/dp.py)."""
     require_cuda(ptrs, offs, sizes, flat)
-    check(lib().tavsr_bucket_copy(ptr(ptrs), ptr(offs), ptr(sizes), int(n), ptr(flat), C.c_float(scale), int(bool(to_flat)),
-                                  C.c_int64(max_n), stream()), "tavsr_bucket_copy")
+    check(lib().tavsr_bucket_copy(ptr(ptrs), ptr(offs), ptr(sizes), int(n), ptr(flat), scale, int(bool(to_flat)), max_n, stream()),
+          "tavsr_bucket_copy")
 
 
 def multi_add_(dst, src):
@@ -1818,9 +1778,9 @@ def video_prep(src, index, T, y0, x0, th, tw, flip, affine, masked, out, pad_val
     n = len(affine)
     mean = (C.c_float * 4)(*[a[0] for a in affine], *([0.0] * (4 - n)))
     std = (C.c_float * 4)(*[a[1] for a in affine], *([1.0] * (4 - n)))
-    check(lib().tavsr_video_prep(ptr(src), int(src.dtype == torch.uint8), Ts, H, W, ptr(frames), int(T), int(y0), int(x0), int(th),
-                                 int(tw), int(bool(flip)), mean, std, n, ptr(m), ptr(ws), ptr(out), int(out.shape[0]),
-                                 C.c_float(pad_value), stream()), "tavsr_video_prep")
+    check(lib().tavsr_video_prep(ptr(src), int(src.dtype == torch.uint8), Ts, H, W, ptr(frames), int(T), int(y0), int(x0), int(th), int(tw),
+                                 int(bool(flip)), mean, std, n, ptr(m), ptr(ws), ptr(out), int(out.shape[0]), pad_value, stream()),
+          "tavsr_video_prep")
     return out
 
 
@@ -1828,8 +1788,7 @@ def add_noise(audio, noise, inv_snr):
     require_cuda(audio, noise)
     assert audio.numel() == noise.numel() and audio.is_contiguous() and noise.is_contiguous()
     out = torch.empty_like(audio)
-    check(lib().tavsr_add_noise(ptr(audio), ptr(noise), ptr(out), C.c_int64(audio.numel()), C.c_float(inv_snr), stream()),
-          "tavsr_add_noise")
+    check(lib().tavsr_add_noise(ptr(audio), ptr(noise), ptr(out), audio.numel(), inv_snr, stream()), "tavsr_add_noise")
     return out
 
 
@@ -1842,12 +1801,10 @@ def resample(audio, factor: float):
     ``factor`` times faster at the same sample rate (tavsr_resample_sinc)"""
     require_cuda(audio)
     x = audio.float().contiguous().view(-1)
-    fn = lib().tavsr_resample_len
-    fn.restype = C.c_int64
-    n_out = int(fn(C.c_int64(x.numel()), C.c_double(factor)))
+    n_out = lib().tavsr_resample_len(x.numel(), factor)
     y = empty(n_out, like=x)
-    check(lib().tavsr_resample_sinc(ptr(x), C.c_int64(x.numel()), ptr(y), C.c_int64(n_out), C.c_double(factor), C.c_double(RESAMPLE_ROLLOFF),
-                                    RESAMPLE_ZEROS, C.c_double(RESAMPLE_BETA), stream()), "tavsr_resample_sinc")
+    check(lib().tavsr_resample_sinc(ptr(x), x.numel(), ptr(y), n_out, factor, RESAMPLE_ROLLOFF, RESAMPLE_ZEROS, RESAMPLE_BETA, stream()),
+          "tavsr_resample_sinc")
     return y.view(*audio.shape[:-1], n_out)
 
 
@@ -1867,7 +1824,7 @@ def bootstrap_rates(dist, reflen, iters, seed):
     require_cuda(dist, reflen)
     assert dist.dtype == torch.int32 and reflen.dtype == torch.int32 and dist.numel() == reflen.numel()
     rates = torch.empty(iters, dtype=torch.float64, device=dist.device)
-    check(lib().tavsr_bootstrap_rates(ptr(dist), ptr(reflen), dist.numel(), int(iters), C.c_uint64(seed), ptr(rates), stream()),
+    check(lib().tavsr_bootstrap_rates(ptr(dist), ptr(reflen), dist.numel(), int(iters), seed, ptr(rates), stream()),
           "tavsr_bootstrap_rates")
     return rates
 
@@ -1919,11 +1876,9 @@ def rowlin(x, w, b=None, *, ln=None, act=None, res=None, out=None, gather=None, 
         assert w.shape[1] == K and out is None
         g, be, eps = ln if ln is not None else (None, None, 0.0)
         o = empty(ksplit, N, Nout, like=xt) if ksplit > 1 else empty(N, Nout, like=xt)
-        check(lib().tavsr_rowlin_parts(ptr(xt), C.c_int64(xt.stride(0)), xp, C.c_int64(x.t.stride(0) if xp > 1 else 0), ptr(g),
-                                       ptr(be), C.c_float(eps), ptr(w), C.c_int64(w.stride(0)), ptr(b), ACT[act], ptr(rt),
-                                       C.c_int64(0 if rt is None else rt.stride(0)), rp, C.c_int64(res.t.stride(0) if rp > 1 else 0),
-                                       ptr(o), C.c_int64(Nout), ksplit, C.c_int64(N * Nout if ksplit > 1 else 0), N, K, Nout,
-                                       stream()), "tavsr_rowlin_parts")
+        check(lib().tavsr_rowlin_parts(ptr(xt), xt.stride(0), xp, x.t.stride(0) if xp > 1 else 0, ptr(g), ptr(be), eps, ptr(w), w.stride(0),
+                                       ptr(b), ACT[act], ptr(rt), 0 if rt is None else rt.stride(0), rp, res.t.stride(0) if rp > 1 else 0,
+                                       ptr(o), Nout, ksplit, N * Nout if ksplit > 1 else 0, N, K, Nout, stream()), "tavsr_rowlin_parts")
         return RowParts(o) if ksplit > 1 else o
     N = x.shape[0] if gather is None else gather.numel()
     K, Nout = x.shape[1], w.shape[0]
@@ -1933,9 +1888,9 @@ def rowlin(x, w, b=None, *, ln=None, act=None, res=None, out=None, gather=None, 
         out = empty(N, Nout, like=x)
     assert out.data_ptr() != x.data_ptr()
     g, be, eps = ln if ln is not None else (None, None, 0.0)
-    check(lib().tavsr_rowlin(ptr(x), C.c_int64(x.stride(0)), ptr(gather), ptr(g), ptr(be), C.c_float(eps), ptr(w),
-                             C.c_int64(w.stride(0)), ptr(b), ACT[act], ptr(res), C.c_int64(0 if res is None else res.stride(0)),
-                             ptr(res_gather), ptr(out), C.c_int64(out.stride(0)), N, K, Nout, stream()), "tavsr_rowlin")
+    check(lib().tavsr_rowlin(ptr(x), x.stride(0), ptr(gather), ptr(g), ptr(be), eps, ptr(w), w.stride(0), ptr(b), ACT[act], ptr(res),
+                             0 if res is None else res.stride(0), ptr(res_gather), ptr(out), out.stride(0), N, K, Nout, stream()),
+          "tavsr_rowlin")
     return out
 
 
@@ -1949,10 +1904,9 @@ def tree_attn_step(q, kpool, vpool, anc, nkeys, H, dk, out=None, step_dev=None, 
     assert k_new is None or (k_new.stride(0) == q.stride(0) and v_new.stride(0) == q.stride(0))
     if out is None:
         out = empty(N, H * dk, like=q)
-    check(lib().tavsr_tree_attn_step(ptr(q), C.c_int64(q.stride(0)), ptr(kpool), ptr(vpool), C.c_int64(kpool.stride(0)),
-                                     ptr(anc), C.c_int64(anc.stride(0)), int(nkeys), ptr(out), C.c_int64(out.stride(0)), N, H, dk,
-                                     C.c_float(1.0 / (dk ** 0.5)), ptr(step_dev), ptr(k_new), ptr(v_new), int(group), stream()),
-          "tavsr_tree_attn_step")
+    check(lib().tavsr_tree_attn_step(ptr(q), q.stride(0), ptr(kpool), ptr(vpool), kpool.stride(0), ptr(anc), anc.stride(0), int(nkeys),
+                                     ptr(out), out.stride(0), N, H, dk, 1.0 / (dk ** 0.5), ptr(step_dev), ptr(k_new), ptr(v_new),
+                                     int(group), stream()), "tavsr_tree_attn_step")
     return out
 
 
@@ -1961,8 +1915,8 @@ def kv_append(k, v, kpool, vpool, N, max_steps, step_dev):
     require_cuda(k, v, kpool, vpool, step_dev)
     assert step_dev.dtype == torch.int32 and k.stride(0) == v.stride(0) and kpool.stride(0) == vpool.stride(0)
     assert kpool.shape[0] >= max_steps * N
-    check(lib().tavsr_kv_append(ptr(k), ptr(v), C.c_int64(k.stride(0)), ptr(kpool), ptr(vpool), C.c_int64(kpool.stride(0)),
-                                N, k.shape[1], int(max_steps), ptr(step_dev), stream()), "tavsr_kv_append")
+    check(lib().tavsr_kv_append(ptr(k), ptr(v), k.stride(0), ptr(kpool), ptr(vpool), kpool.stride(0), N, k.shape[1], int(max_steps),
+                                ptr(step_dev), stream()), "tavsr_kv_append")
 
 
 def ctc_prefix_step(logp, lens, r_prev, s_prev, last_tok, cand, K, out_len, blank=0, step_dev=None):
@@ -2002,7 +1956,7 @@ def act_(x, act):
     """x = act(x) in place."""
     require_cuda(x)
     assert x.is_contiguous()
-    check(lib().tavsr_act_fwd(ptr(x), ptr(x), C.c_int64(x.numel()), ACT[act], stream()), "tavsr_act_fwd")
+    check(lib().tavsr_act_fwd(ptr(x), ptr(x), x.numel(), ACT[act], stream()), "tavsr_act_fwd")
     return x
 
 
@@ -2014,8 +1968,8 @@ def log_softmax_rows(x, V=None, out=None, alpha=1.0, add=0.0, accumulate=False):
     if out is None:
         out = empty(M, V, like=x)
     assert not accumulate or out is not None
-    check(lib().tavsr_log_softmax_rows(ptr(x), C.c_int64(x.stride(0)), ptr(out), C.c_int64(out.stride(0)), M, V, C.c_float(alpha),
-                                       C.c_float(add), int(bool(accumulate)), stream()), "tavsr_log_softmax_rows")
+    check(lib().tavsr_log_softmax_rows(ptr(x), x.stride(0), ptr(out), out.stride(0), M, V, alpha, add, int(bool(accumulate)), stream()),
+          "tavsr_log_softmax_rows")
     return out
 
 
@@ -2026,7 +1980,7 @@ def beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, eos, w
     require_cuda(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score)
     weighted = empty(N, V, like=full)
     check(lib().tavsr_beam_combine(ptr(full), ptr(cand), ptr(psi), ptr(psi_abs), ptr(eos_s), ptr(eos_abs), ptr(s_prev), ptr(score),
-                                   ptr(weighted), N, V, Cn, int(eos), C.c_float(w_ctc), stream()), "tavsr_beam_combine")
+                                   ptr(weighted), N, V, Cn, int(eos), w_ctc, stream()), "tavsr_beam_combine")
     return weighted
 
 
@@ -2043,7 +1997,7 @@ def beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, e
     top_i = torch.empty(N // K, K, dtype=torch.int64, device=full.device)
     weighted = empty(N, V, like=full) if keep_weighted else None
     check(lib().tavsr_beam_combine_topk(ptr(full), ptr(cand), ptr(psi), ptr(psi_abs), ptr(eos_s), ptr(eos_abs), ptr(s_prev), ptr(score),
-                                        ptr(weighted), ptr(top_s), ptr(top_i), N, K, V, Cn, int(eos), C.c_float(w_ctc), stream()),
+                                        ptr(weighted), ptr(top_s), ptr(top_i), N, K, V, Cn, int(eos), w_ctc, stream()),
           "tavsr_beam_combine_topk")
     return (top_s, top_i, weighted) if keep_weighted else (top_s, top_i)
 
@@ -2063,9 +2017,9 @@ def beam_select_topk(dec, z_lm, w_lm, add, psi_all, psi_abs_all, eos_s, eos_abs,
     full = empty(N, V, like=dec) if keep else None
     weighted = empty(N, V, like=dec) if keep else None
     cand = torch.empty(N, Cn, dtype=torch.int64, device=dec.device) if keep else None
-    check(lib().tavsr_beam_select_topk(ptr(dec), ptr(z_lm), C.c_float(w_lm), C.c_float(add), ptr(psi_all), ptr(psi_abs_all), ptr(eos_s),
-                                       ptr(eos_abs), ptr(s_prev), ptr(score), ptr(full), ptr(weighted), ptr(cand), ptr(top_s), ptr(top_i),
-                                       N, K, V, int(Cn), int(eos), C.c_float(w_ctc), stream()), "tavsr_beam_select_topk")
+    check(lib().tavsr_beam_select_topk(ptr(dec), ptr(z_lm), w_lm, add, ptr(psi_all), ptr(psi_abs_all), ptr(eos_s), ptr(eos_abs),
+                                       ptr(s_prev), ptr(score), ptr(full), ptr(weighted), ptr(cand), ptr(top_s), ptr(top_i), N, K, V,
+                                       int(Cn), int(eos), w_ctc, stream()), "tavsr_beam_select_topk")
     return (top_s, top_i, full, weighted, cand) if keep else (top_s, top_i)
 
 
@@ -2163,8 +2117,7 @@ def dropout(x, p: float, out=None, token=None):
     n = x.numel()
     if token is None:
         token = _new_token(p, n, x.device)
-    check(lib().tavsr_dropout(ptr(x), ptr(out), C.c_int64(n), C.c_float(token[0]), ptr(token[2]),
-                              C.c_uint64(token[1]), stream()), "tavsr_dropout")
+    check(lib().tavsr_dropout(ptr(x), ptr(out), n, token[0], ptr(token[2]), token[1], stream()), "tavsr_dropout")
     return out, token
 
 
@@ -2176,8 +2129,7 @@ def dropout_add(a, t, p: float, alpha: float = 1.0, out=None):
         out = torch.empty_like(a)
     n = t.numel()
     token = _new_token(p, n, a.device)
-    check(lib().tavsr_dropout_add(ptr(a), ptr(t), ptr(out), C.c_int64(n), C.c_float(p), C.c_float(alpha),
-                                  ptr(token[2]), C.c_uint64(token[1]), stream()), "tavsr_dropout_add")
+    check(lib().tavsr_dropout_add(ptr(a), ptr(t), ptr(out), n, p, alpha, ptr(token[2]), token[1], stream()), "tavsr_dropout_add")
     return out, token
 
 
@@ -2187,6 +2139,6 @@ def dropout_act_bwd(dh, z, act, token, out=None):
     assert dh.is_contiguous() and z.is_contiguous() and dh.numel() == z.numel()
     if out is None:
         out = torch.empty_like(dh)
-    check(lib().tavsr_dropout_act_bwd(ptr(dh), ptr(z), ptr(out), C.c_int64(dh.numel()), C.c_float(token[0]), ACT[act],
-                                      ptr(token[2]), C.c_uint64(token[1]), stream()), "tavsr_dropout_act_bwd")
+    check(lib().tavsr_dropout_act_bwd(ptr(dh), ptr(z), ptr(out), dh.numel(), token[0], ACT[act], ptr(token[2]), token[1], stream()),
+          "tavsr_dropout_act_bwd")
     return out

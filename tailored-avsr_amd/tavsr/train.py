@@ -12,7 +12,6 @@
 """
 from __future__ import annotations
 
-import ctypes as C
 from typing import Iterable, List, Optional
 
 import torch
@@ -88,12 +87,9 @@ class FusedAdam:
         for ia, ib in runs:
             lo = self.offsets[ia]
             hi = self.offsets[ib + 1] if ib + 1 < len(self.params) else self.flat.numel()
-            L.check(L.lib().tavsr_adamw_step(C.c_void_p(L.addr(self.flat, lo)), C.c_void_p(L.addr(self.grad, lo)),
-                                             C.c_void_p(L.addr(self.exp_avg, lo)),
-                                             C.c_void_p(L.addr(self.exp_avg_sq, lo)), C.c_int64(hi - lo),
-                                             C.c_float(g["lr"]), C.c_float(g["betas"][0]), C.c_float(g["betas"][1]),
-                                             C.c_float(g["eps"]), C.c_float(g.get("weight_decay", 0.0)),
-                                             C.c_int64(self._steps[ia]), C.c_float(grad_scale), L.stream()),
+            L.check(L.lib().tavsr_adamw_step(L.addr(self.flat, lo), L.addr(self.grad, lo), L.addr(self.exp_avg, lo),
+                                             L.addr(self.exp_avg_sq, lo), hi - lo, g["lr"], g["betas"][0], g["betas"][1],
+                                             g["eps"], g.get("weight_decay", 0.0), self._steps[ia], grad_scale, L.stream()),
                     "tavsr_adamw_step")
 
     def state_dict(self):

@@ -319,8 +319,8 @@ def test_rccl_c_abi_single_rank_roundtrip():
     want = x.clone()
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
-    check(lib().tavsr_dp_allreduce(C.c_void_p(x.data_ptr()), C.c_int64(x.numel()), C.c_void_p(s.cuda_stream)), "tavsr_dp_allreduce")
-    check(lib().tavsr_dp_broadcast(C.c_void_p(x.data_ptr()), C.c_int64(x.numel()), 0, C.c_void_p(s.cuda_stream)), "tavsr_dp_broadcast")
+    check(lib().tavsr_dp_allreduce(x.data_ptr(), x.numel(), s.cuda_stream), "tavsr_dp_allreduce")
+    check(lib().tavsr_dp_broadcast(x.data_ptr(), x.numel(), 0, s.cuda_stream), "tavsr_dp_broadcast")
     s.synchronize()
     assert torch.equal(x, want)
     check(lib().tavsr_dp_destroy(), "tavsr_dp_destroy")

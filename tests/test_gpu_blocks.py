@@ -132,11 +132,9 @@ def test_conv2d_subsample_block_vs_fp64_and_the_launches(B, T, Fq, Cn, odim):
 def test_workspace_bytes_is_the_per_entry_query_times_four():
     from tavsr._lib import BfLayerDesc, GemmDesc, SubsampleDesc, lib
     fn = lib().tavsr_workspace_bytes
-    fn.restype = C.c_int64
     d = BfLayerDesc()
     d.B, d.T, d.D, d.H, d.ffn_units, d.cg_units, d.cg_kernel = 4, 99, 256, 4, 2048, 2048, 31
     per = lib().tavsr_branchformer_layer_ws
-    per.restype = C.c_int64
     assert fn(2, C.byref(d)) == 4 * per(C.byref(d)) > 0
     g = GemmDesc()
     g.M, g.N, g.K, g.nb1, g.nb2 = 256, 2048, 3168, 1, 1

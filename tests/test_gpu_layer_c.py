@@ -67,7 +67,6 @@ def test_layer_in_c_is_used_and_refuses_foreign_shapes():
     d = BfLayerDesc()
     d.B, d.T, d.D, d.H, d.ffn_units, d.cg_units, d.cg_kernel = 2, 50, 512, 8, 2048, 2048, 31
     fn = lib().tavsr_branchformer_layer_ws
-    fn.restype = C.c_int64
     assert fn(C.byref(d)) == 0
     assert lib().tavsr_branchformer_layer_fwd(C.byref(d), None) != 0
     d.D, d.H = 256, 4
