@@ -716,6 +716,31 @@ int tavsr_maskctc_step(const float* logits, int64_t ld_l, int64_t ld_b, int64_t*
                        int32_t V1, tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Mask-CTC training: the MLM input / target pair drawn on the device (src/models/maskctc_model.py:216-241, espnet
+ * maskctc/add_mask_token.py:mask_uniform).  One workgroup per utterance, no host value read, no allocation: capturable,
+ * and a captured step draws new masks at every replay because the seed is device data (as tavsr_dropout).
+ *   For row b of text [B][ld_text]: the tokens are the entries != ignore_id among the first Lmax, IN ORDER wherever they sit
+ *   (the host function filters them the same way); len is their count.  ys_in[b][0:len] = the tokens, ys_in[b][len:Lmax] =
+ *   eos, ys_out[b][0:Lmax] = ignore_id; then n = randint(1, len + 1) positions drawn uniformly WITH replacement are masked:
+ *   ys_out[b][idx] = token, ys_in[b][idx] = mask_token.  The distribution is the reference's, the random stream is not
+ *   numpy's: utterance b owns the counters [offset + b*S, offset + (b+1)*S) with S = (Lmax + 1 + 3) / 4 * 4, counter c
+ *   is word (c & 3) of philox4x32_10(counter = c / 4, key = seed_dev[0]) (the mapping of tavsr_dropout), and with
+ *   base = offset + b*S:  n = 1 + mulhi_u32(word(base), len),  idx_j = mulhi_u32(word(base + 1 + j), len) for j < n.
+ *   mulhi_u32(w, len) = (w * len) >> 32 deviates from the uniform distribution on [0, len) by less than len / 2^32 per value.
+ *   n_target[b] (may be NULL) = the number of DISTINCT masked positions = the non-ignored entries of ys_out[b].
+ *   Every element of both output rows up to Lmax is written, padding included.  An utterance without tokens (len == 0)
+ *   gives a row of padding and n_target[b] = 0 (the host function raises inside numpy for such a row).
+ *   Lmax <= TAVSR_MASK_UNIFORM_MAX_L, else TAVSR_EUNSUPPORTED before anything is launched.
+ *   count_recip: inv[0] = 1 / max(1, sum_{b < B} n[b]) (integer sum, one fp32 division): the denominator of the
+ *   length-normalised MLM loss when only the device knows the target count.
+ * ------------------------------------------------------------------------------------------- */
+enum { TAVSR_MASK_UNIFORM_MAX_L = 4096 };
+int tavsr_mask_uniform(const int64_t* text, int64_t ld_text, int32_t B, int32_t Lmax, int32_t mask_token, int32_t eos,
+                       int32_t ignore_id, const uint64_t* seed_dev, uint64_t offset, int64_t* ys_in, int64_t* ys_out,
+                       int64_t ld_y, int32_t* n_target, tavsr_stream_t stream);
+int tavsr_count_recip(const int32_t* n, int32_t B, float* inv, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Attention-decoder loss side (espnet LabelSmoothingLoss + th_accuracy, espnet_model.py:553-569)
  * and decoder input embedding (Embedding + PositionalEncoding, espnet transformer_decoder.py).
  *   lsm_loss: row_loss[r] = KL(smoothed one-hot || softmax(logits[r])) (0 for ignored rows),

@@ -5,6 +5,9 @@
 //   maskctc_step : one pass of the fill loop (:331-334, last pass :340) on the decoder's logits
 // One workgroup per utterance, per-utterance state in LDS, integer outputs: bit-exact contract.  No host value is read or
 // written, so a whole decode loop is one stream of launches (capturable).
+// Mask-CTC training (src/models/maskctc_model.py:216-241, espnet maskctc/add_mask_token.py:mask_uniform):
+//   mask_uniform : the MLM input / target pair of a batch, drawn on the device from the dropout generator's counter stream
+//   count_recip  : 1 / max(1, sum of the per-utterance target counts) - the length-normalised loss's denominator
 #include <float.h>
 #include <math.h>
 
@@ -174,6 +177,78 @@ __global__ __launch_bounds__(256) void maskctc_step_kernel(const float* __restri
   }
 }
 
+// word (c & 3) of philox4x32_10(counter = c / 4, key = seed): the counter -> word mapping of dropout.hip
+__device__ __forceinline__ uint32_t mc_word(uint64_t c, uint64_t seed) {
+  const uint64_t ctr = c >> 2;
+  uint32_t r[4];
+  philox4x32_10((uint32_t)ctr, (uint32_t)(ctr >> 32), 0u, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+  const int k = (int)(c & 3);      // (selects, not a dynamically indexed register array)
+  return k == 0 ? r[0] : k == 1 ? r[1] : k == 2 ? r[2] : r[3];
+}
+
+// Dynamic LDS: Lmax ints (column of text the compacted token l came from) + Lmax ints (mask flags).
+// The draws are WITH replacement: several j may hit one position, all of them store the same 1 (idempotent), and one pass
+// afterwards writes both rows - every element of ys_in[b][0:Lmax] and ys_out[b][0:Lmax] exactly once, padding included.
+__global__ __launch_bounds__(256) void mask_uniform_kernel(const int64_t* __restrict__ text, int64_t ld_text, int Lmax,
+                                                           int mask_token, int eos, int ignore_id,
+                                                           const uint64_t* __restrict__ seed, uint64_t offset, uint64_t S,
+                                                           int64_t* __restrict__ ys_in, int64_t* __restrict__ ys_out,
+                                                           int64_t ld_y, int32_t* __restrict__ n_target) {
+  extern __shared__ int mc_sm[];
+  int* s_src = mc_sm;
+  int* s_flag = mc_sm + Lmax;
+  __shared__ int s_cnt[257];
+  __shared__ int s_masks;
+  const int b = blockIdx.x, tid = threadIdx.x;
+  const int64_t* row = text + (int64_t)b * ld_text;
+  const int per = (Lmax + 255) / 256;
+  const int l0 = min(Lmax, tid * per), l1 = min(Lmax, l0 + per);
+  int cnt = 0;
+  for (int l = l0; l < l1; ++l) cnt += row[l] != (int64_t)ignore_id;
+  s_cnt[tid + 1] = cnt;
+  if (tid == 0) { s_cnt[0] = 0; s_masks = 0; }
+  for (int l = tid; l < Lmax; l += 256) s_flag[l] = 0;
+  __syncthreads();
+  mc_scan256(s_cnt, tid);
+  __syncthreads();
+  int pos = s_cnt[tid];
+  const int len = s_cnt[256];
+  for (int l = l0; l < l1; ++l)
+    if (row[l] != (int64_t)ignore_id) s_src[pos++] = l;
+  if (len > 0) {
+    const uint64_t sd = seed[0], base = offset + (uint64_t)b * S;
+    const int n = 1 + (int)__umulhi(mc_word(base, sd), (uint32_t)len);      // randint(1, len + 1)
+    for (int j = tid; j < n; j += 256) s_flag[__umulhi(mc_word(base + 1 + (uint64_t)j, sd), (uint32_t)len)] = 1;
+  }
+  __syncthreads();
+  int64_t* yi = ys_in + (int64_t)b * ld_y;
+  int64_t* yo = ys_out + (int64_t)b * ld_y;
+  int masks = 0;
+  for (int l = tid; l < Lmax; l += 256) {
+    const bool real = l < len;
+    const bool masked = real && s_flag[l];
+    const int64_t tok = real ? row[s_src[l]] : (int64_t)eos;
+    yi[l] = masked ? (int64_t)mask_token : tok;
+    yo[l] = masked ? tok : (int64_t)ignore_id;
+    masks += masked;
+  }
+  if (n_target) {
+    if (masks) atomicAdd(&s_masks, masks);      // (integer, in LDS: the sum does not depend on the order)
+    __syncthreads();
+    if (tid == 0) n_target[b] = s_masks;
+  }
+}
+
+// inv[0] = 1 / max(1, sum_b n[b]) by one wave: integer sum, one fp32 division
+__global__ __launch_bounds__(64) void count_recip_kernel(const int32_t* __restrict__ n, int B, float* __restrict__ inv) {
+  const int lane = threadIdx.x;
+  int s = 0;
+  for (int b = lane; b < B; b += 64) s += n[b];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if (lane == 0) inv[0] = 1.f / (float)(s > 1 ? s : 1);
+}
+
 }  // namespace tavsr
 
 using namespace tavsr;
@@ -207,6 +282,28 @@ extern "C" int tavsr_maskctc_step(const float* logits, int64_t ld_l, int64_t ld_
   TAVSR_REQUIRE(lds <= 60000, TAVSR_EUNSUPPORTED, "maskctc_step: L=%d exceeds the LDS budget of the candidate table", L);
   hipLaunchKernelGGL(maskctc_step_kernel, dim3(B), dim3(256), lds, (hipStream_t)stream, logits, ld_l, ld_b, y_in, ld_y, y_len,
                      plan, it, mask_token, L, V1);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
+extern "C" int tavsr_mask_uniform(const int64_t* text, int64_t ld_text, int32_t B, int32_t Lmax, int32_t mask_token,
+                                  int32_t eos, int32_t ignore_id, const uint64_t* seed_dev, uint64_t offset, int64_t* ys_in,
+                                  int64_t* ys_out, int64_t ld_y, int32_t* n_target, tavsr_stream_t stream) {
+  TAVSR_REQUIRE(Lmax >= 0 && ld_text >= Lmax && ld_y >= Lmax, TAVSR_EINVAL, "mask_uniform: ld_text, ld_y >= Lmax >= 0 required");
+  TAVSR_REQUIRE(Lmax <= TAVSR_MASK_UNIFORM_MAX_L, TAVSR_EUNSUPPORTED,
+                "mask_uniform: Lmax=%d exceeds the kernel's limit of %d tokens per row", Lmax, TAVSR_MASK_UNIFORM_MAX_L);
+  TAVSR_REQUIRE(B <= 0 || (seed_dev && (Lmax == 0 || (text && ys_in && ys_out))), TAVSR_EINVAL, "mask_uniform: null pointer");
+  if (B <= 0) return TAVSR_OK;
+  const uint64_t S = ((uint64_t)Lmax + 1 + 3) / 4 * 4;
+  hipLaunchKernelGGL(mask_uniform_kernel, dim3(B), dim3(256), (size_t)(Lmax > 0 ? Lmax : 1) * 8, (hipStream_t)stream, text,
+                     ld_text, Lmax, mask_token, eos, ignore_id, seed_dev, offset, S, ys_in, ys_out, ld_y, n_target);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
+extern "C" int tavsr_count_recip(const int32_t* n, int32_t B, float* inv, tavsr_stream_t stream) {
+  TAVSR_REQUIRE(inv && (n || B <= 0), TAVSR_EINVAL, "count_recip: null pointer");
+  hipLaunchKernelGGL(count_recip_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, n, B > 0 ? B : 0, inv);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
 }

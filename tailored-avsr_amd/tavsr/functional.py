@@ -1254,12 +1254,21 @@ _DEC_WGRAD = int(os.environ.get("TAVSR_DEC_WGRAD", "5"))     # layers between tw
 
 
 class LabelSmoothingLossFn(torch.autograd.Function):
-    """espnet LabelSmoothingLoss (KL, sum / batch) on decoder logits; also yields the th_accuracy counters."""
+    """espnet LabelSmoothingLoss (KL, sum / batch) on decoder logits; also yields the th_accuracy counters.
+    ``count`` (optional, [n] int32 on the device; used with ``normalize_length``): the number of real target tokens as per-row
+    counts that only the device knows (ops.mask_uniform's ``n_target``) - the loss is sum / max(1, sum(count)) with the
+    reciprocal formed on the device in fp32, so nothing is read on the host and the step stays capturable."""
 
     @staticmethod
-    def forward(ctx, logits, target, ignore, smoothing, normalize_length):
+    def forward(ctx, logits, target, ignore, smoothing, normalize_length, count=None):
         B, L, V = logits.shape
         row, g, correct = ops.lsm_loss(logits.reshape(B * L, V), target.reshape(-1).contiguous(), ignore, smoothing)
+        ctx.mark_non_differentiable(correct)
+        if normalize_length and count is not None:
+            inv = ops.count_recip(count)
+            ctx.save_for_backward(g, inv)
+            ctx.B, ctx.denom = B, None
+            return ops.scale_dev(ops.colsum(row.view(-1, 1)), inv).view(()), correct
         denom = B
         if normalize_length:      # espnet LabelSmoothingLoss: sum / number of real target tokens (a host count, as espnet's .item())
             if logits.is_cuda and torch.cuda.is_current_stream_capturing():
@@ -1267,14 +1276,17 @@ class LabelSmoothingLossFn(torch.autograd.Function):
             denom = max(1, int((target != ignore).sum()))
         ctx.save_for_backward(g)
         ctx.B, ctx.denom = B, denom
-        ctx.mark_non_differentiable(correct)
         return ops.colsum(row.view(-1, 1), scale=1.0 / denom).view(()), correct
 
     @staticmethod
     @guarded
     def backward(ctx, dl, _dc):
+        if ctx.denom is None:
+            g, inv = ctx.saved_tensors
+            s = ops.scale_dev(dl.reshape(1).contiguous(), inv)
+            return ops.scale_dev(g, s).view(ctx.B, -1, g.shape[-1]), None, None, None, None, None
         (g,) = ctx.saved_tensors
-        return ops.scale_dev(g, dl.contiguous(), 1.0 / ctx.denom).view(ctx.B, -1, g.shape[-1]), None, None, None, None
+        return ops.scale_dev(g, dl.contiguous(), 1.0 / ctx.denom).view(ctx.B, -1, g.shape[-1]), None, None, None, None, None
 
 
 class WeightedSumFn(torch.autograd.Function):

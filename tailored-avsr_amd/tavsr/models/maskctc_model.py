@@ -2,8 +2,10 @@
 ``model: maskctc`` with ``decoder: mlm``).
 
 Training: the encoder, the CTC branch and the intermediate-CTC mix are the parent's; the decoder branch is the MLM loss
-(``mask_uniform`` on the host, ``MLMDecoder``, label smoothing over the vocabulary with ``<mask>``).  Decoding: the token
-bookkeeping of ``MaskCTCInference.forward`` is two kernels (``ops.maskctc_init`` / ``ops.maskctc_step``), so a batch is
+(``mask_uniform``, ``MLMDecoder``, label smoothing over the vocabulary with ``<mask>``).  The masks are drawn on the host from
+numpy's generator as the reference draws them (``mask_draw = "host"``, the default), or on the device from the dropout
+generator (``mask_draw = "device"``: ``ops.mask_uniform``, no host round trip, capturable with new masks per replay).
+Decoding: the token bookkeeping of ``MaskCTCInference.forward`` is two kernels (``ops.maskctc_init`` / ``ops.maskctc_step``), so a batch is
 decoded with one host read before the loop and one after it; every utterance follows its own iteration plan, i.e. comes out
 as if it were decoded alone."""
 from __future__ import annotations
@@ -50,16 +52,33 @@ class _MaskCTCMixin:
         self.error_calculator = (ErrorCalculator(self.token_list, sym_space, sym_blank, report_cer, report_wer)
                                  if (report_cer or report_wer) else None)
 
+    # where the MLM masks are drawn: "host" (numpy's global generator in the reference's call order: a run seeded like the
+    # reference draws its masks, but every step reads ``text`` on the host) or "device" (ops.mask_uniform: the reference's
+    # distribution from the device generator's counter stream - the step makes no host round trip and can be captured, and
+    # data-parallel ranks, seeded base + rank, draw different masks as they draw different dropout).  An attribute, not a
+    # constructor argument: the constructors keep the reference's signatures.
+    mask_draw = "host"
+    last_mask_token = None      # introspection: the token of the last device draw (ops.mask_uniform(text, ..., token=) redraws it)
+
     def _decoder_branch(self, encoder_out, encoder_out_lens, text, text_lengths, ys_in_pad=None, ys_out_pad=None, **kwargs):
         loss_mlm = acc_mlm = None
         if self.ctc_weight != 1.0:
+            count = None
             if ys_in_pad is None or ys_out_pad is None:      # (a caller may draw the masks itself, off the critical path)
-                if text.is_cuda and torch.cuda.is_current_stream_capturing():
-                    raise NotImplementedError("mask_uniform draws on the host: pass ys_in_pad / ys_out_pad to a captured step")
-                ys_in_pad, ys_out_pad = mask_uniform(text, self.mask_token, self.eos, self.ignore_id)
+                if self.mask_draw == "device":
+                    ys_in_pad, ys_out_pad, n_target, self.last_mask_token = ops.mask_uniform(
+                        text.contiguous(), self.mask_token, self.eos, self.ignore_id)
+                    count = n_target if self.length_normalized_loss else None
+                elif self.mask_draw == "host":
+                    if text.is_cuda and torch.cuda.is_current_stream_capturing():
+                        raise NotImplementedError("mask_uniform draws on the host: set mask_draw = \"device\" or pass ys_in_pad / "
+                                                  "ys_out_pad to a captured step")
+                    ys_in_pad, ys_out_pad = mask_uniform(text, self.mask_token, self.eos, self.ignore_id)
+                else:
+                    raise ValueError(f"mask_draw must be \"host\" or \"device\", got {self.mask_draw!r}")
             decoder_out, _ = self.decoder(encoder_out, encoder_out_lens, ys_in_pad.to(text.device), text_lengths)
             loss_mlm, correct = self.criterion_mlm.apply(decoder_out, ys_out_pad.to(text.device).to(torch.int64), self.ignore_id,
-                                                         self.lsm_weight, self.length_normalized_loss)
+                                                         self.lsm_weight, self.length_normalized_loss, count)
             acc_mlm = _Accuracy(correct)
         return loss_mlm, {"loss_mlm": loss_mlm.detach() if loss_mlm is not None else None, "acc_mlm": acc_mlm}
 

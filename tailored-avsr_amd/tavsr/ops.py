@@ -1382,6 +1382,34 @@ def maskctc_step(logits, y_in, y_len, plan, it, mask_token):
     return y_in
 
 
+def mask_uniform(text, mask_token, eos, ignore_id, token=None):
+    """text [B, L] int64 -> (ys_in, ys_out [B, L] int64, n_target [B] int32, token): espnet ``mask_uniform`` drawn on the device
+    (tavsr_mask_uniform; include/tavsr.h has the counter layout).  ``token`` follows the dropout contract: (offset, step-seed
+    tensor), a fresh one reserves B * S counters of the current pass; a call with a previous token regenerates that draw bit
+    for bit.  No host read, no sync: capturable, and a captured call draws new masks at every replay."""
+    require_cuda(text)
+    assert text.dim() == 2 and text.dtype == torch.int64 and (text.shape[1] <= 1 or text.stride(1) == 1)
+    B, Lmax = text.shape
+    if token is None:
+        _, off, seed = _new_token(0.0, B * ((Lmax + 1 + 3) // 4 * 4), text.device)
+        token = (off, seed)
+    ys_in = torch.empty((B, Lmax), dtype=torch.int64, device=text.device)
+    ys_out = torch.empty((B, Lmax), dtype=torch.int64, device=text.device)
+    n_target = torch.empty((B,), dtype=torch.int32, device=text.device)
+    check(lib().tavsr_mask_uniform(ptr(text), text.stride(0), B, Lmax, int(mask_token), int(eos), int(ignore_id), ptr(token[1]),
+                                   token[0], ptr(ys_in), ptr(ys_out), Lmax, ptr(n_target), stream()), "tavsr_mask_uniform")
+    return ys_in, ys_out, n_target, token
+
+
+def count_recip(n):
+    """n [B] int32 on the device -> 1 / max(1, sum(n)) as a one-element fp32 device tensor (tavsr_count_recip)."""
+    require_cuda(n)
+    assert n.dtype == torch.int32 and n.is_contiguous()
+    inv = torch.empty((1,), dtype=f32, device=n.device)
+    check(lib().tavsr_count_recip(ptr(n), n.numel(), ptr(inv), stream()), "tavsr_count_recip")
+    return inv
+
+
 def lsm_loss(logits2d, target, ignore, smoothing):
     rows, V = logits2d.shape
     require_cuda(logits2d, target)
