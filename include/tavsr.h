@@ -120,7 +120,18 @@ typedef struct tavsr_gemm_desc {
                     [2 ho - 3 + kh][2 wo - 3 + kw] (0 outside the clip / frame, 0 for k >= 245); B = weights [Cout][256];
        conv_mode 5: B is X (TN layout, a_kmajor and b_kmajor), N = 256, K = output pixels (a multiple of 32): weight gradient
                     dW[co][tap] = sum_m dY[m][co] * patch(m, tap); columns >= 245 come out 0.
-     lda (mode 4) / ldb (mode 5) are ignored (pass a multiple of 4). */
+     lda (mode 4) / ldb (mode 5) are ignored (pass a multiple of 4).
+     conv_posmajor (non-zero; honoured for conv_mode 1 without a_rowsum and conv_mode 2, with the 9 padded taps at stride 1;
+     IGNORED everywhere else - the launch is then exactly the one without it): skip the multiplications by padding.
+       conv_mode 1: the tiles walk the rows position-major (virtual row r = position * images + image, positions ordered
+         interior, edges, corners; only the loader's and the epilogue's addresses know - every operand stays where it is),
+         so that the rows of a tile share their pixel position and the K-steps of the taps that fall into the padding for
+         ALL of them are neither fetched nor multiplied.  The remaining K-steps keep their order and their K split: the
+         result is bit-identical to conv_posmajor = 0.
+       conv_mode 2: a K slice holds whole images (slices of lcm(H*W, 32) pixels) and walks its pixels position-major; a
+         K-step where the tile's tap is padding at every position it covers is passed over.  Every pixel is summed once for
+         every tap, in another order than with conv_posmajor = 0; a_rowsum is taken by the centre tap's tile, which skips
+         nothing.  tavsr_gemm_ws answers for the descriptor as given: ask it with the flag set. */
   int32_t conv_mode, conv_H, conv_W, conv_C;
   const float* conv_zero;
   int32_t conv_stride, conv_taps;
@@ -131,6 +142,7 @@ typedef struct tavsr_gemm_desc {
      its backward mask * act'(z)).  Unbatched plain GEMMs on the 16-byte path only (N % 4 == 0, aligned operands,
      K % 32 == 0 or the K-tail variant): otherwise TAVSR_EUNSUPPORTED and nothing is launched. */
   float drop_p;
+  int32_t conv_posmajor;          /* see the conv fields above; it sits in what was padding, so no other field moves */
   const uint64_t* drop_seed;
   uint64_t drop_offset;
   /* optional [M][ceil(N / 64)][2]: per row and 64-column tile, sum and sum of squares of the stored C values (after bias /

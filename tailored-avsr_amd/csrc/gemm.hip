@@ -207,12 +207,48 @@ __device__ __forceinline__ void read_frag(const float* __restrict__ s, int row, 
   }
 }
 
+// Position-major virtual rows of an implicit 3x3 / stride 1 / pad 1 convolution (tavsr_gemm_desc.conv_posmajor): virtual row
+// r = v * n + image, where v counts the H x W pixel positions interior first (9 taps inside the image), then the edges (6), then
+// the corners (4) - the tiles with the most K-steps are dispatched first.  A tile whose rows share one position (uni) maps its
+// rows without a division.
+struct PosMajor {
+  int n, H, W;          // images, map
+  int uni, base, rp;    // the tile lies on ONE position: its virtual rows start at base = v * n, rp = y * W + x
+  __device__ __forceinline__ void pos(int v, int& y, int& x) const {
+    const int Hi = max(H - 2, 0), Wi = max(W - 2, 0), Hb = H - Hi, Wb = W - Wi;       // interior / border coordinates
+    int u = v;
+    if (u < Hi * Wi) { y = u / Wi + 1; x = u % Wi + 1; return; }
+    u -= Hi * Wi;
+    if (u < Hi * Wb) { y = u / Wb + 1; x = (u % Wb) ? W - 1 : 0; return; }
+    u -= Hi * Wb;
+    if (u < Hb * Wi) { y = (u / Wi) ? H - 1 : 0; x = u % Wi + 1; return; }
+    u -= Hb * Wi;
+    y = (u / Wb) ? H - 1 : 0;
+    x = (u % Wb) ? W - 1 : 0;
+  }
+  __device__ __forceinline__ uint32_t taps(int y, int x) const {      // bit tap: the tap's neighbour of (y, x) is inside the image
+    uint32_t mk = 0;
+#pragma unroll
+    for (int tap = 0; tap < 9; ++tap)
+      mk |= (uint32_t)((unsigned)(y + tap / 3 - 1) < (unsigned)H && (unsigned)(x + tap % 3 - 1) < (unsigned)W) << tap;
+    return mk;
+  }
+  __device__ __forceinline__ int row(int r) const {                   // the real row (image * H * W + y * W + x) of virtual row r
+    if (uni) return (r - base) * (H * W) + rp;
+    const int v = r / n;
+    int y, x;
+    pos(v, y, x);
+    return (r - v * n) * (H * W) + y * W + x;
+  }
+};
+
 // Common tail of both kernels: lane pairs complete the row sums, then either the split-K slab store or the fused
 // epilogue.  Accumulator layout: lane owns column (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5).
-template <int TM, int TN>
+template <int TM, int TN, bool PM = false>
 __device__ __forceinline__ void finish_tile(const tavsr_gemm_desc& d, int nsplit, f32x16 (&acc)[TM][TN],
                                             float (&asum)[TM], bool want_rowsum, int m0, int n0, int wm, int wn, int lr,
-                                            int lk, int z1, int z2, int64_t coff, int zidx, const float* bias_pre = nullptr) {
+                                            int lk, int z1, int z2, int64_t coff, int zidx, const float* bias_pre = nullptr,
+                                            const PosMajor* pm = nullptr) {
   if (want_rowsum) {
 #pragma unroll
     for (int i = 0; i < TM; ++i) asum[i] += __shfl_xor(asum[i], 32, 64);
@@ -235,7 +271,7 @@ __device__ __forceinline__ void finish_tile(const tavsr_gemm_desc& d, int nsplit
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int m = mb + (r & 3) + 8 * (r >> 2);
-          if (m < d.M) slab[(int64_t)m * d.N + n] = acc[i][j][r];
+          if (m < d.M) slab[(int64_t)(PM ? pm->row(m) : m) * d.N + n] = acc[i][j][r];
         }
       }
     }
@@ -271,8 +307,9 @@ __device__ __forceinline__ void finish_tile(const tavsr_gemm_desc& d, int nsplit
       const int mb = m0 + wm * TM * 32 + i * 32 + 4 * lk;
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        const int m = mb + (r & 3) + 8 * (r >> 2);
-        if (m >= d.M) continue;
+        const int mv = mb + (r & 3) + 8 * (r >> 2);
+        if (mv >= d.M) continue;
+        const int m = PM ? pm->row(mv) : mv;
         float v = acc[i][j][r] + bv;
         const int64_t o = (int64_t)m * d.ldc + n;
         if (Z) Z[o] = v;
@@ -443,10 +480,10 @@ void gemm_kernel(const GemmArgs args) {
 // covers whole 256-byte row segments instead of 2 x 128 bytes, and a 64x64 tile with a pre-activation output issues 8
 // store instructions per lane instead of 32.  At K = 256 the old per-register epilogue was a third of a block's life
 // (profiles/r01_gemm_trace.txt).  Needs N % 4 == 0 and 16-byte aligned rows of every output / epilogue operand.
-template <int BM, int BN, int NT, int TM, int TN>
+template <int BM, int BN, int NT, int TM, int TN, bool PM = false>
 __device__ __forceinline__ void finish_tile_vec(const tavsr_gemm_desc& d, int nsplit, f32x16 (&acc)[TM][TN], float* __restrict__ img,
                                                 int m0, int n0, int wm, int wn, int lr, int lk, int z1, int z2, int64_t coff,
-                                                int tid, int zidx) {
+                                                int tid, int zidx, const PosMajor* pm = nullptr) {
   __syncthreads();                                   // every wave has finished reading the staging ring
 #pragma unroll
   for (int i = 0; i < TM; ++i)
@@ -475,8 +512,9 @@ __device__ __forceinline__ void finish_tile_vec(const tavsr_gemm_desc& d, int ns
 #pragma unroll
   for (int q = 0; q < PER; ++q) {
     const int idx = q * NT + tid, row = idx / V4R, c4 = idx % V4R;
-    const int m = m0 + row, n = n0 + 4 * c4;
-    const bool ok = m < d.M && n < d.N;
+    const int mv = m0 + row, n = n0 + 4 * c4;
+    const bool ok = mv < d.M && n < d.N;
+    const int m = PM && ok ? pm->row(mv) : mv;       // conv_posmajor: every row-addressed access below takes the real row
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     if (ok) {
     v = *reinterpret_cast<const float4*>(img + row * BN + 4 * c4);
@@ -519,7 +557,7 @@ __device__ __forceinline__ void finish_tile_vec(const tavsr_gemm_desc& d, int ns
       }
 #pragma unroll
       for (int o2 = 8; o2 > 0; o2 >>= 1) { s1 += __shfl_xor(s1, o2, 64); s2 += __shfl_xor(s2, o2, 64); }
-      if (c4 == 0 && m < d.M)
+      if (c4 == 0 && mv < d.M)
         *reinterpret_cast<float2*>(d.rowstat + ((int64_t)m * ((d.N + 63) / 64) + n0 / 64) * 2) = make_float2(s1, s2);
     }
   }
@@ -637,7 +675,8 @@ __device__ unsigned int g_trace_n;
 // operand is fetched with the GEMM's ordinary 16-byte LDS-DMA (two per thread and K-step instead of eight 4-byte gathers; the
 // source is only 8-byte aligned, which gfx950's global_load_lds takes) and no validity test is left:
 //   6: A(m, k) = xp[clip][t + kt][2 ho + kh][2 wo + kw];   7: B(k = pixel, n = tap) likewise (weight gradient).
-template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0>
+// PM (CONV 1, 3x3 / stride 1 / pad 1 only): position-major virtual rows, K-steps of all-padding taps skipped (struct PosMajor).
+template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
 __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, int nsplit, int tiles_n, int bid, bool vec_epi,
                                           int zidx) {
   constexpr int BK = 32, NG = BK / 8;
@@ -650,6 +689,7 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   constexpr int NR4A = BM * BK / NT, NR4B = BN * BK / NT;      // 4-byte gathers per thread per tile (CONV 4 / 5)
   constexpr int G = (CONV == 4 ? NR4A : LA::NR) + (CONV == 5 ? NR4B : LB::NR);          // LDS-DMA instructions per wave per tile
   static_assert((S - 2) * G <= 63, "vmcnt field");
+  static_assert(!PM || (KW == 1 && ((CONV == 1 && !AK) || (CONV == 2 && AK && BKM))), "position-major order: the 3x3 convolution's GEMMs");
   __shared__ __attribute__((aligned(1024))) float smem[S * STAGE];
 
   const int tid = threadIdx.x;
@@ -677,7 +717,8 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   float asum[TM];
 #pragma unroll
   for (int i = 0; i < TM; ++i) asum[i] = 0.f;
-  const bool want_rowsum = d.a_rowsum != nullptr && n0 == 0 && wn == 0;
+  // (position-major weight gradient: the centre tap's tile is the one that skips no pixel)
+  const bool want_rowsum = d.a_rowsum != nullptr && n0 == (PM && CONV == 2 ? 4 * d.conv_C : 0) && wn == 0;
   float bpre[TN];      // the epilogue's bias values, fetched under the K loop instead of in front of the stores
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -687,7 +728,7 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
 
   const int kbeg = zidx * kchunk;
   const int kend = min(d.K, kbeg + kchunk);
-  const int nk = CONV == 3 ? (kend - kbeg + BK - 1) / BK : (kend - kbeg) / BK;     // whole K-steps (host guarantees it); CONV 3: K tail
+  int nk = CONV == 3 ? (kend - kbeg + BK - 1) / BK : (kend - kbeg) / BK;     // whole K-steps (host guarantees it); CONV 3: K tail
   const int64_t kstepA = AK ? (int64_t)BK * d.lda : BK;
   const int64_t kstepB = BKM ? (int64_t)BK * d.ldb : BK;
   int64_t offA[LA::NR], offB[LB::NR];
@@ -702,7 +743,51 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   // centred on input pixel (cs*ho + 1, cs*wo + 1) and every tap is inside the image
   const int cp0 = (CONV == 1 || CONV == 2) && d.conv_taps == 90 ? 1 : 0;
   const int cHo = CONV ? (d.conv_H - 1 - 2 * cp0) / cs + 1 : 1, cWo = CONV ? (d.conv_W - 1 - 2 * cp0) / cs + 1 : 1;
-  if (CONV == 1) {
+  // PM: the tile's tap set pm_taps = OR over the positions its rows span (workgroup-uniform); the ring runs over the K-steps of
+  // these taps only, in their old order.  (pm_tap, pm_cb) = tap and 32-channel block of the next step to issue.
+  PosMajor pm{};
+  uint32_t pm_taps = 0;
+  int pm_tap = 0, pm_cb = 0;
+  if (PM && CONV == 1) {
+    pm.H = d.conv_H; pm.W = d.conv_W;
+    pm.n = d.M / (d.conv_H * d.conv_W);
+    const int vlo = m0 / pm.n, vhi = min(m0 + BM - 1, d.M - 1) / pm.n;
+    for (int v = vlo; v <= vhi; ++v) {
+      int y, x;
+      pm.pos(v, y, x);
+      pm_taps |= pm.taps(y, x);
+      pm.rp = y * d.conv_W + x;
+    }
+    pm.uni = vlo == vhi;
+    pm.base = vlo * pm.n;
+    nk = 0;
+    for (int tap = 0; tap < 9; ++tap) {               // the K-steps of this slice that lie in a tap of the set
+      const int lo = max(kbeg, tap * d.conv_C), hi = min(kend, (tap + 1) * d.conv_C);
+      if (((pm_taps >> tap) & 1u) && hi > lo) nk += (hi - lo) / BK;
+    }
+    pm_tap = kbeg / d.conv_C;
+    pm_cb = (kbeg - pm_tap * d.conv_C) / BK;
+    if (!((pm_taps >> pm_tap) & 1u)) {
+      const uint32_t up = pm_taps >> (pm_tap + 1) << (pm_tap + 1);
+      pm_tap = up ? __builtin_ctz(up) : 9;
+      pm_cb = 0;
+    }
+#pragma unroll
+    for (int i = 0; i < LA::NR; ++i) {
+      const int q = i * NT + tid, row = q >> 3;
+      const int r = min(m0 + row, d.M - 1);
+      int y, x, img;
+      if (pm.uni) {
+        y = pm.rp / d.conv_W; x = pm.rp - y * d.conv_W; img = r - pm.base;
+      } else {
+        const int v = r / pm.n;
+        pm.pos(v, y, x);
+        img = r - v * pm.n;
+      }
+      offA[i] = ((int64_t)img * (d.conv_H * d.conv_W) + y * d.conv_W + x) * d.lda + ((q & 7) ^ ((row >> 1) & 7)) * 4;
+      cmask[i] = pm.taps(y, x);
+    }
+  } else if (CONV == 1) {
 #pragma unroll
     for (int i = 0; i < LA::NR; ++i) {
       const int m = min(m0 + ((i * NT + tid) >> 3), d.M - 1);
@@ -819,6 +904,43 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
       c2_oy[i] = t - c2_img[i] * cHo;
     }
   }
+  // PM, CONV 2: K is the pixel axis and a K slice holds whole images (plan_conv), p2_n of them from image p2_i0 on.  The slice is
+  // walked position-major: step k' covers pixel position k' / p2_n (row-major, y * W + x) of image p2_i0 + k' % p2_n, so 32
+  // consecutive k' share their position (or straddle a few) and the steps at whose positions this tile's tap is padding are
+  // passed over: neither fetched nor multiplied.  Every pixel of the slice is still summed exactly once for every tap.
+  // (p2_v = y * W + x, p2_img): where the next candidate step starts - workgroup-uniform.
+  int p2_n = 1, p2_i0 = 0, p2_v = 0, p2_img = 0, p2_x = 0, p2_y = 0;
+  auto p2_ok = [&](int y, int x) {
+    return (unsigned)(y + c2_dy) < (unsigned)d.conv_H && (unsigned)(x + c2_dx) < (unsigned)d.conv_W;
+  };
+  auto p2_advance = [&]() {
+    p2_img += BK;
+    while (p2_img >= p2_n) {
+      p2_img -= p2_n;
+      ++p2_v;
+      if (++p2_x == d.conv_W) { p2_x = 0; ++p2_y; }
+    }
+  };
+  if (PM && CONV == 2) {
+    const int P = d.conv_H * d.conv_W;
+    p2_i0 = kbeg / P;
+    p2_n = (kend - kbeg) / P;
+#pragma unroll
+    for (int i = 0; i < LA::NR; ++i) offA[i] -= (int64_t)((i * NT + tid) / (BM / 4)) * d.lda;      // the row part; k is gathered
+    if (p2_n % BK == 0) {       // every step lies on one position
+      nk = (p2_n / BK) * max(d.conv_H - abs(c2_dy), 0) * max(d.conv_W - abs(c2_dx), 0);
+    } else {                    // the steps that touch a position where the tap is inside the image
+      nk = 0;
+      int prev = 0, y = 0, x = 0;
+      for (int v = 0; v < P; ++v) {
+        if (p2_ok(y, x)) {
+          const int s_lo = max(v * p2_n / BK, prev), s_hi = ((v + 1) * p2_n - 1) / BK + 1;
+          if (s_hi > s_lo) { nk += s_hi - s_lo; prev = s_hi; }
+        }
+        if (++x == d.conv_W) { x = 0; ++y; }
+      }
+    }
+  }
   // CONV 3 (K tail: K % 32 != 0): chunks whose first k lies at or past K are fetched from a zero page; a k-contiguous chunk
   // that straddles K (K % 4 != 0) is fetched whole and its k >= K elements are zeroed in LDS before the last K-step
   int kofsA[LA::NR], kofsB[LB::NR];
@@ -835,6 +957,56 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
     }
   }
   auto issue = [&](int kt, int st) {
+    if (PM && CONV == 2) {
+      for (;;) {              // pass the steps whose tap is padding at every position they touch
+        bool any = false;
+        int end = p2_img + BK, y = p2_y, x = p2_x;
+        for (;;) {
+          any |= p2_ok(y, x);
+          if (end <= p2_n) break;
+          end -= p2_n;
+          if (++x == d.conv_W) { x = 0; ++y; }
+        }
+        if (any) break;
+        p2_advance();
+      }
+      const int P = d.conv_H * d.conv_W;
+      auto locate = [&](int kl, int& y, int& x) {        // pixel of the step's k row kl, and its position
+        int img = p2_img + kl, v = p2_v;
+        y = p2_y; x = p2_x;
+        while (img >= p2_n) {
+          img -= p2_n;
+          ++v;
+          if (++x == d.conv_W) { x = 0; ++y; }
+        }
+        return (int64_t)(p2_i0 + img) * P + v;
+      };
+#pragma unroll
+      for (int i = 0; i < LA::NR; ++i) {
+        int y, x;
+        const int64_t pix = locate((i * NT + tid) / (BM / 4), y, x);
+        __builtin_amdgcn_global_load_lds((glb_float*)(A + pix * d.lda + offA[i]), (lds_float*)(smem + st * STAGE + (i * NT + wave * 64) * 4), 16, 0, 0);
+      }
+#pragma unroll
+      for (int i = 0; i < LB::NR; ++i) {
+        const int r = (((i * NT + tid) % (BN / 4)) * 4);
+        int y, x;
+        const int64_t pix = locate((i * NT + tid) / (BN / 4), y, x);
+        const float* src = p2_ok(y, x) ? B + (pix + c2_tapoff) * d.conv_C + c2_cb + r : d.conv_zero;
+        __builtin_amdgcn_global_load_lds((glb_float*)src, (lds_float*)(smem + st * STAGE + ASZ + (i * NT + wave * 64) * 4), 16, 0, 0);
+      }
+      p2_advance();
+      return;
+    }
+    int kpm = 0, kpm_tap = 0;         // PM: the k and the tap of this (compacted) step
+    if (PM) {
+      kpm_tap = pm_tap;
+      kpm = pm_tap * d.conv_C + pm_cb * BK;
+      const int wrap = (pm_cb + 1) * BK >= d.conv_C;
+      const uint32_t up = pm_taps >> (pm_tap + 1) << (pm_tap + 1);
+      pm_cb = wrap ? 0 : pm_cb + 1;
+      pm_tap = !wrap ? pm_tap : up ? __builtin_ctz(up) : 9;
+    }
     if (CONV == 3) {
       const int kleft = kend - (kbeg + kt * BK);                 // k values of this step that exist
 #pragma unroll
@@ -873,7 +1045,7 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
         __builtin_amdgcn_global_load_lds((glb_float*)src, (lds_float*)(smem + st * STAGE + i * NT + wave * 64), 4, 0, 0);
       }
     } else if (CONV == 1) {
-      const int kk = kbeg + kt * BK, tap = kk / d.conv_C;
+      const int kk = PM ? kpm : kbeg + kt * BK, tap = PM ? kpm_tap : kk / d.conv_C;
       const int toff = c9 ? (tap / 3 - 1) * d.conv_W + (tap % 3 - 1) : 0;
       const int64_t delta = (int64_t)toff * d.conv_C + (kk - tap * d.conv_C);
 #pragma unroll
@@ -938,6 +1110,8 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
         oy -= w2 ? cHo : 0;
         c2_ox[i] = ox; c2_oy[i] = oy; c2_img[i] += c2_sahi + w2;
       }
+    } else if (PM) {
+      LB::issue(B + (BKM ? (int64_t)kpm * d.ldb : kpm), offB, smem + st * STAGE + ASZ, wave);
     } else {
       LB::issue(Bk + kt * kstepB, offB, smem + st * STAGE + ASZ, wave);
     }
@@ -1065,9 +1239,9 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
         }
       }
     }
-    finish_tile_vec<BM, BN, NT, TM, TN>(d, nsplit, acc, smem, m0, n0, wm, wn, lr, lk, z1, z2, coff, tid, zidx);
+    finish_tile_vec<BM, BN, NT, TM, TN, PM && CONV == 1>(d, nsplit, acc, smem, m0, n0, wm, wn, lr, lk, z1, z2, coff, tid, zidx, &pm);
   } else {
-    finish_tile<TM, TN>(d, nsplit, acc, asum, want_rowsum, m0, n0, wm, wn, lr, lk, z1, z2, coff, zidx, bpre);
+    finish_tile<TM, TN, PM && CONV == 1>(d, nsplit, acc, asum, want_rowsum, m0, n0, wm, wn, lr, lk, z1, z2, coff, zidx, bpre, &pm);
   }
 #ifdef TAVSR_GEMM_TRACE
   __builtin_amdgcn_s_waitcnt(0);
@@ -1089,7 +1263,7 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
-template <int BM, int BN, int WM, int WN, int S, int MINW, bool AK, bool BKM, int KW = 1, int CONV = 0>
+template <int BM, int BN, int WM, int WN, int S, int MINW, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
 __global__ __launch_bounds__(WM* WN * KW * 64, MINW)
 void gemm_glds_kernel(const GemmArgs args) {
   int bid = xcd_remap(blockIdx.x, gridDim.x), zidx = blockIdx.z;
@@ -1103,7 +1277,7 @@ void gemm_glds_kernel(const GemmArgs args) {
     zidx = (l & 7) + 8 * (j / tiles);
     bid = j % tiles;
   }
-  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx);
+  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx);
 }
 
 // Grouped launch: up to kMaxGroup independent problems of one layout share ONE grid (tile ranges by prefix sums).
@@ -1265,6 +1439,12 @@ static int launch_glds(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
   return rc ? rc : launch_epilogue(a, s);
 }
 
+// tavsr_gemm_desc.conv_posmajor applies: 3x3 / stride 1 / pad 1, forward / data gradient (no row sums there) or weight gradient
+static bool conv_pm(const tavsr_gemm_desc& d) {
+  return d.conv_posmajor && (d.conv_mode == 1 || d.conv_mode == 2) && d.conv_stride <= 1 && (d.conv_taps == 0 || d.conv_taps == 9) &&
+         (d.conv_mode == 2 || !d.a_rowsum);
+}
+
 // implicit-convolution launches (two-stage 64x64 variant): mode 1 = A patches (NT / NN), mode 2 = B patches (TN)
 static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStream_t s) {
   const int ve = (int)vec_epi_ok(d);
@@ -1310,24 +1490,39 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
     TAVSR_LAUNCH_CHECK();
     return launch_epilogue(a4, s);
   }
+  // conv_posmajor: honoured for the 9 padded taps at stride 1 (ignored elsewhere, include/tavsr.h): same tiles; forward / data
+  // gradient keep their K split, the weight gradient's slices are whole images (plan_conv)
+  const bool pm = conv_pm(d) && d.conv_mode == 1, pm2 = conv_pm(d) && d.conv_mode == 2;
   if (d.conv_mode == 1 && !d.b_kmajor && nsplit == 1 && wide && d.N % 128 == 0) {
     GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 128), (int)vec_epi_ok(d)};
-    hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, a2);
+    if (pm)
+      hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1, true>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, a2);
+    else
+      hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, a2);
     TAVSR_LAUNCH_CHECK();
     return TAVSR_OK;
   }
   if (d.conv_mode == 2 && dw_wide && d.M % 128 == 0) {     // weight gradient: 128 output channels share one patch tile
     GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 128), cdiv(d.N, 64), (int)vec_epi_ok(d), zmap};
-    hipLaunchKernelGGL((gemm_glds_kernel<128, 64, 2, 2, 2, 3, true, true, 1, 2>), dim3(a2.tiles_m * a2.tiles_n, 1, nsplit), dim3(256), 0, s, a2);
+    if (pm2)
+      hipLaunchKernelGGL((gemm_glds_kernel<128, 64, 2, 2, 2, 3, true, true, 1, 2, true>), dim3(a2.tiles_m * a2.tiles_n, 1, nsplit), dim3(256), 0, s, a2);
+    else
+      hipLaunchKernelGGL((gemm_glds_kernel<128, 64, 2, 2, 2, 3, true, true, 1, 2>), dim3(a2.tiles_m * a2.tiles_n, 1, nsplit), dim3(256), 0, s, a2);
     TAVSR_LAUNCH_CHECK();
     return launch_epilogue(a2, s);
   }
   GemmArgs a{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 64), ve, zmap};
   dim3 grid(a.tiles_m * a.tiles_n, 1, nsplit);
-  if (d.conv_mode == 1 && !d.b_kmajor)
+  if (pm && !d.b_kmajor)
+    hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, false, 1, 1, true>), grid, dim3(256), 0, s, a);
+  else if (pm)
+    hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, true, 1, 1, true>), grid, dim3(256), 0, s, a);
+  else if (d.conv_mode == 1 && !d.b_kmajor)
     hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, false, 1, 1>), grid, dim3(256), 0, s, a);
   else if (d.conv_mode == 1)
     hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, true, 1, 1>), grid, dim3(256), 0, s, a);
+  else if (pm2)
+    hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, true, true, 1, 2, true>), grid, dim3(256), 0, s, a);
   else
     hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, true, true, 1, 2>), grid, dim3(256), 0, s, a);
   TAVSR_LAUNCH_CHECK();
@@ -1433,14 +1628,27 @@ static Plan plan_conv(const tavsr_gemm_desc& d, bool can_split) {
     constexpr long target64 = 2560L;
     constexpr long target128 = 2304L;
     const long target = wide ? target128 : target64;
+    // position-major weight gradient: a slice holds whole images and whole K-steps (it is walked position-major inside, so a
+    // tap's tile costs the same in every slice and the XCDs stay balanced): slices of lcm(H * W, 32) pixels
+    int unit = 32;
+    if (conv_pm(d)) {
+      const int P = d.conv_H * d.conv_W;
+      int g = P, b = 32;
+      while (b) { const int t = g % b; g = b; b = t; }
+      unit = P / g * 32;
+      if (pc.nsplit > 1) {
+        pc.kchunk = cdiv(pc.kchunk, unit) * unit;
+        pc.nsplit = cdiv(d.K, pc.kchunk);
+      }
+    }
     const long want = std::min<long>(std::max<long>(1, target / tiles), d.K / 512);
     if (want > pc.nsplit) {
-      pc.kchunk = cdiv(cdiv(d.K, want), 32) * 32;
+      pc.kchunk = cdiv(cdiv(d.K, want), unit) * unit;
       pc.nsplit = cdiv(d.K, pc.kchunk);
     }
     if (pc.nsplit >= 16 && pc.nsplit % 8 != 0) {        // a multiple of 8 slices lets launch_conv keep each slice on one XCD
       for (long w8 = pc.nsplit / 8 * 8; w8 >= 8; w8 -= 8) {
-        const int kc = cdiv(cdiv(d.K, w8), 32) * 32;
+        const int kc = cdiv(cdiv(d.K, w8), unit) * unit;
         if (cdiv(d.K, kc) % 8 == 0) { pc.kchunk = kc; pc.nsplit = cdiv(d.K, kc); break; }
         if (w8 < pc.nsplit / 2) break;
       }

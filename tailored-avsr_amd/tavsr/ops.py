@@ -102,6 +102,8 @@ def gemm(M, N, K, A, lda, B, ldb, Cc, ldc, *, a_off=0, b_off=0, c_off=0, a_kmajo
         d.conv_mode, d.conv_H, d.conv_W, d.conv_C = conv[:4]
         if len(conv) > 4:
             d.conv_stride, d.conv_taps = conv[4], conv[5]
+        if len(conv) > 6:
+            d.conv_posmajor = int(conv[6])
         d.conv_zero = _addr(_zero_page(Cc.device))
     if force is not None and force[1] > 1:
         need = force[1] * max(1, nb1) * max(1, nb2) * M * N + force[1] * M
@@ -1649,6 +1651,19 @@ def conv_wflip(w2d, cout, cin):
     return out
 
 
+# Padding taps of the stride-1 3x3 / pad 1 convolutions (tavsr_gemm_desc.conv_posmajor): forward and data gradient walk their
+# rows position-major and skip the K-steps of the taps that are padding for a whole tile (bit-identical results); the weight
+# gradient walks the pixels of a K slice position-major and skips the steps where its tile's tap is padding.  Applied to maps
+# of at most CONV_TAPSKIP_MAXPOS positions (trunk layers 3 and 4: 6x6 and 3x3; on the 11x11 and 22x22 maps of layers 2 and 1 a
+# few per cent of the taps are padding).  TAVSR_CONV_TAPSKIP=0: today's launches (A/B switch).
+CONV_TAPSKIP = os.environ.get("TAVSR_CONV_TAPSKIP", "1") != "0"
+CONV_TAPSKIP_MAXPOS = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS", "36"))
+
+
+def _tapskip(H, W, stride=1, taps=9, pad0=False):
+    return int(CONV_TAPSKIP and stride == 1 and taps == 9 and not pad0 and H * W <= CONV_TAPSKIP_MAXPOS)
+
+
 def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None):
     """implicit 3x3/p1 (taps 9) or 1x1/p0 (taps 1) convolution with stride: x [images*H*W, Cin] channels-last image rows,
     w2d [Cout, taps*Cin] -> [images*Ho*Wo, Cout].  ``pad0``: the 3x3 window without padding (Conv2dSubsampling)."""
@@ -1661,7 +1676,8 @@ def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None)
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     Mo = M // (H * W) * Ho * Wo
     z = empty(Mo, cout, like=x)
-    gemm(Mo, cout, taps * cin, x, cin, w2d, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps), bias=bias, act=act)
+    gemm(Mo, cout, taps * cin, x, cin, w2d, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps, _tapskip(H, W, stride, taps, pad0)),
+         bias=bias, act=act)
     return z
 
 
@@ -1671,7 +1687,7 @@ def conv3x3_dx(dz, wflip, H, W, res=None):
     M, cout = dz.shape
     cin = wflip.shape[0]
     dx = empty(M, cin, like=dz)
-    gemm(M, cin, 9 * cout, dz, cout, wflip, 9 * cout, dx, cin, conv=(1, H, W, cout), R=res, ldr=0 if res is None else cin)
+    gemm(M, cin, 9 * cout, dz, cout, wflip, 9 * cout, dx, cin, conv=(1, H, W, cout, 0, 0, _tapskip(H, W)), R=res, ldr=0 if res is None else cin)
     return dx
 
 
@@ -1683,7 +1699,7 @@ def conv3x3_dw(dz, x, H, W, stride=1, taps=9, pad0=False, bias_grad=False):
     dw = empty(cout, taps * cin, like=dz)
     gb = empty(cout, like=dz) if bias_grad else None
     gemm(cout, taps * cin, M, dz, cout, x, cin, dw, taps * cin, a_kmajor=True, b_kmajor=True,
-         conv=(2, H, W, cin, stride, 90 if pad0 else taps), a_rowsum=gb)
+         conv=(2, H, W, cin, stride, 90 if pad0 else taps, _tapskip(H, W, stride, taps, pad0)), a_rowsum=gb)
     return (dw, gb) if bias_grad else dw
 
 
