@@ -131,7 +131,12 @@ typedef struct tavsr_gemm_desc {
        conv_mode 2: a K slice holds whole images (slices of lcm(H*W, 32) pixels) and walks its pixels position-major; a
          K-step where the tile's tap is padding at every position it covers is passed over.  Every pixel is summed once for
          every tap, in another order than with conv_posmajor = 0; a_rowsum is taken by the centre tap's tile, which skips
-         nothing.  tavsr_gemm_ws answers for the descriptor as given: ask it with the flag set. */
+         nothing.  tavsr_gemm_ws answers for the descriptor as given: ask it with the flag set.
+       Bit 1 (value 3 instead of 1) keeps the tiles in their plain order (A/B aid): without it the forward / data gradient
+       tiles are sorted by tap count and dealt evenly to the XCDs (launches without a K split, maps whose sorted order
+       fits 80 runs of m-tiles; otherwise the plain order), and the weight gradient hands out a slice's tiles heaviest tap
+       first where every K slice runs on one XCD (a multiple of 8 slices; otherwise the plain order).  The same tiles either
+       way: results do not depend on the bit. */
   int32_t conv_mode, conv_H, conv_W, conv_C;
   const float* conv_zero;
   int32_t conv_stride, conv_taps;

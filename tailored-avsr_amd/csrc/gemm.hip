@@ -28,6 +28,7 @@
 // of a 64x64 tile over 24 slices by ONE workgroup serialises ~400 KB of reads - profiles/r01_gemm_sweep_v2.txt.)
 #include <algorithm>
 #include <type_traits>
+#include <vector>
 
 #include <cstdlib>
 #include "common.h"
@@ -214,8 +215,8 @@ __device__ __forceinline__ void read_frag(const float* __restrict__ s, int row, 
 struct PosMajor {
   int n, H, W;          // images, map
   int uni, base, rp;    // the tile lies on ONE position: its virtual rows start at base = v * n, rp = y * W + x
-  __device__ __forceinline__ void pos(int v, int& y, int& x) const {
-    const int Hi = max(H - 2, 0), Wi = max(W - 2, 0), Hb = H - Hi, Wb = W - Wi;       // interior / border coordinates
+  __host__ __device__ __forceinline__ void pos(int v, int& y, int& x) const {
+    const int Hi = H > 2 ? H - 2 : 0, Wi = W > 2 ? W - 2 : 0, Hb = H - Hi, Wb = W - Wi;       // interior / border coordinates
     int u = v;
     if (u < Hi * Wi) { y = u / Wi + 1; x = u % Wi + 1; return; }
     u -= Hi * Wi;
@@ -226,7 +227,7 @@ struct PosMajor {
     y = (u / Wb) ? H - 1 : 0;
     x = (u % Wb) ? W - 1 : 0;
   }
-  __device__ __forceinline__ uint32_t taps(int y, int x) const {      // bit tap: the tap's neighbour of (y, x) is inside the image
+  __host__ __device__ __forceinline__ uint32_t taps(int y, int x) const {      // bit tap: the tap's neighbour of (y, x) is inside the image
     uint32_t mk = 0;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
@@ -241,6 +242,61 @@ struct PosMajor {
     return (r - v * n) * (H * W) + y * W + x;
   }
 };
+
+// Tile order of the position-major forward / data gradient.  The hardware deals the workgroups of a launch to the 8 XCDs
+// round-robin (workgroup b runs on XCD b % 8 as its (b / 8)-th), and xcd_remap hands every XCD one contiguous range of tiles.
+// Position-major rows put the 9-tap positions first and the 4-tap corners last, so contiguous ranges give the first XCD only
+// 9-tap tiles and the last only 4-tap ones: the launch lasts as long as the unskipped one on the first XCD, whatever the others
+// skip (profiles/r07_notes.md).  Here the m-tiles are SORTED by falling tap count (a tile that straddles positions has the OR
+// of their taps, so the virtual order alone is not sorted) and dealt in rounds of 8 m-tiles: in a round of equal tap counts
+// XCD x takes the x-th m-tile with all its n-tiles back to back (they share the tile's image rows in that XCD's L2); a round
+// of mixed counts and the last, partial round are dealt tile by tile.  Every XCD then runs its heaviest tiles first and the
+// XCDs' tap totals differ by less than one 9-tap tile (mixed rounds are falling sequences dealt round-robin: the differences
+// telescope).  The host describes the sorted order as runs of consecutive m-tiles of one tap count (at most 2 per position);
+// the tile contents and their K order do not change, so results stay bit-identical.
+constexpr int kOrdRuns = 80;
+struct TileOrder {
+  int nruns;                 // 0: no order given, the launch keeps xcd_remap's
+  int start[kOrdRuns];       // run i: m-tiles start[i] ... of w[i] taps, runs ordered by falling w
+  int cum[kOrdRuns + 1];     // m-tiles in the runs before run i
+  int w[kOrdRuns];
+};
+
+// workgroup b of a grid of tiles_m * tiles_n -> its tile (mt, nt); a permutation of the tiles (tests/test_gpu_conv_tileorder.py)
+__host__ __device__ inline void tile_order_map(const TileOrder& o, int b, int tiles_m, int tiles_n, int& mt, int& nt) {
+  const int per = 8 * tiles_n;                      // workgroups of a round: 8 m-tiles
+  const int g = b / per, j = b - g * per, s0 = 8 * g;
+  int r0 = 0;                                       // run of sorted m-tile s0
+  while (r0 + 1 < o.nruns && o.cum[r0 + 1] <= s0) ++r0;
+  bool uniform = s0 + 8 <= tiles_m;
+  if (uniform) {
+    int r7 = r0;
+    while (r7 + 1 < o.nruns && o.cum[r7 + 1] <= s0 + 7) ++r7;
+    uniform = o.w[r7] == o.w[r0];
+  }
+  const int s = s0 + (uniform ? (j & 7) : j / tiles_n);
+  nt = uniform ? (j >> 3) : j % tiles_n;
+  int r = r0;
+  while (r + 1 < o.nruns && o.cum[r + 1] <= s) ++r;
+  mt = o.start[r] + s - o.cum[r];
+}
+
+// Position-major weight gradient: the q-th tile a K slice hands out.  A slice's tiles run on one XCD (zmap), three per CU, and a
+// tile's K-steps go with the positions at which its tap is inside the map: (H - |dy|) (W - |dx|), 9 / 6 / 4 on a 3x3 map.  In
+// the plain order (row block, tap, channel block) the centre tap's tiles start in the middle of every row block and the XCD
+// waits for the last of them; here the taps go out heaviest first (centre, the two edge pairs, corners), each for all row
+// blocks.  Same tiles, same K order inside each: bit-identical.  Applied where a slice's tiles share an XCD (zmap: a multiple of 8
+// slices) and the column tiles are whole taps (conv_C % 64 == 0, which the launch requires, so tiles_n = 9 channel blocks; any
+// other tiles_n keeps the plain order, and a tiles_n % 9 == 0 that is not whole taps would still be a permutation of the tiles).
+__host__ __device__ inline int dw_tile_order(int q, int tiles_m, int tiles_n, int H, int W) {
+  if (tiles_n % 9 != 0) return q;
+  const int tpt = tiles_n / 9, per = tiles_m * tpt;
+  const int rank = q / per, rem = q - rank * per;
+  // taps by falling weight, one per nibble: 4, then (1, 7) = (H - 1) W and (3, 5) = H (W - 1), the larger first, then the corners
+  const unsigned long long taps = (H - 1) * W >= H * (W - 1) ? 0x862053714ull : 0x862071534ull;
+  const int tap = (int)((taps >> (4 * rank)) & 15);
+  return (rem / tpt) * tiles_n + tap * tpt + rem % tpt;
+}
 
 // Common tail of both kernels: lane pairs complete the row sums, then either the split-K slab store or the fused
 // epilogue.  Accumulator layout: lane owns column (lane&31), rows (r&3) + 8*(r>>2) + 4*(lane>>5).
@@ -1251,7 +1307,7 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
     if (slot < (unsigned)kTraceMax) {
       for (int i = 0; i < 4; ++i) g_trace[slot][i] = tr_t[i];
       g_trace[slot][4] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | __builtin_amdgcn_s_getreg((31 << 11) | 4);
-      g_trace[slot][5] = tr_c[2] - tr_c[1];      // shader-clock cycles of the K loop
+      g_trace[slot][5] = ((tr_c[2] - tr_c[1]) & 0xFFFFFFFFFFull) | ((unsigned long long)nk << 40);      // K loop: shader-clock cycles, K-steps executed above bit 40
     }
   }
 #endif
@@ -1263,10 +1319,26 @@ __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
 }
 
+// (the position-major forward / data gradient launches carry their tile order behind the common arguments)
+struct GemmArgsOrd {
+  GemmArgs g;
+  TileOrder ord;
+};
+__device__ __forceinline__ const GemmArgs& common_args(const GemmArgs& a) { return a; }
+__device__ __forceinline__ const GemmArgs& common_args(const GemmArgsOrd& a) { return a.g; }
+
 template <int BM, int BN, int WM, int WN, int S, int MINW, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
 __global__ __launch_bounds__(WM* WN * KW * 64, MINW)
-void gemm_glds_kernel(const GemmArgs args) {
+void gemm_glds_kernel(const std::conditional_t<PM && CONV == 1, GemmArgsOrd, GemmArgs> xargs) {
+  const GemmArgs& args = common_args(xargs);
   int bid = xcd_remap(blockIdx.x, gridDim.x), zidx = blockIdx.z;
+  if constexpr (PM && CONV == 1) {
+    if (xargs.ord.nruns > 0) {          // tiles sorted by tap count, dealt evenly to the XCDs (struct TileOrder)
+      int mt, nt;
+      tile_order_map(xargs.ord, blockIdx.x, args.tiles_m, args.tiles_n, mt, nt);
+      bid = mt * args.tiles_n + nt;
+    }
+  }
   if (args.zmap) {
     // Workgroups go to the XCDs round-robin in launch order (x fastest, then z).  The tiles of one K slice of a convolution
     // weight gradient read the same dY rows and overlapping image rows (one tile per tap / channel block): give ALL tiles
@@ -1276,6 +1348,9 @@ void gemm_glds_kernel(const GemmArgs args) {
     const int tiles = gridDim.x, l = blockIdx.x + tiles * blockIdx.z, j = l >> 3;
     zidx = (l & 7) + 8 * (j / tiles);
     bid = j % tiles;
+    if constexpr (PM && CONV == 2) {
+      if (!(args.d.conv_posmajor & 2)) bid = dw_tile_order(bid, args.tiles_m, args.tiles_n, args.d.conv_H, args.d.conv_W);
+    }
   }
   glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx);
 }
@@ -1445,6 +1520,51 @@ static bool conv_pm(const tavsr_gemm_desc& d) {
          (d.conv_mode == 2 || !d.a_rowsum);
 }
 
+// The sorted tile order of a position-major forward / data gradient launch with BM-row tiles (struct TileOrder).  nruns stays 0,
+// and the launch keeps its old order, for a K split (the grid's z axis moves the workgroups' XCDs), where conv_posmajor's bit 1
+// asks for it (A/B aid: ops.CONV_TILEORDER) and on a map with more runs than the table holds.
+static void tile_order_build(const tavsr_gemm_desc& d, int BM, int nsplit, TileOrder& o) {
+  o.nruns = 0;
+  const int P = d.conv_H * d.conv_W;
+  if (nsplit != 1 || (d.conv_posmajor & 2) || P <= 0 || d.M < P) return;
+  // the order depends on (H, W, M, BM) alone and a step repeats a handful of them: keep the last one built per thread
+  struct Key { int H, W, M, BM; };
+  static thread_local Key last{0, 0, 0, 0};
+  static thread_local TileOrder last_o;
+  if (last.H == d.conv_H && last.W == d.conv_W && last.M == d.M && last.BM == BM) { o = last_o; return; }
+  PosMajor pm{};
+  pm.H = d.conv_H; pm.W = d.conv_W; pm.n = d.M / P;
+  std::vector<uint32_t> tp(P);
+  for (int v = 0; v < P; ++v) {
+    int y, x;
+    pm.pos(v, y, x);
+    tp[v] = pm.taps(y, x);
+  }
+  struct Run { int start, len, w; };
+  std::vector<Run> runs;
+  const int tiles_m = cdiv(d.M, BM);
+  for (int i = 0; i < tiles_m; ++i) {
+    const int vlo = (int)((int64_t)i * BM / pm.n);
+    const int vhi = std::min((int)(std::min<int64_t>((int64_t)i * BM + BM - 1, d.M - 1) / pm.n), P - 1);    // (M = whole images: already so)
+    uint32_t mk = 0;
+    for (int v = vlo; v <= vhi; ++v) mk |= tp[v];
+    const int w = __builtin_popcount(mk);
+    if (!runs.empty() && runs.back().w == w) ++runs.back().len;
+    else runs.push_back(Run{i, 1, w});
+    if ((int)runs.size() > kOrdRuns) return;
+  }
+  std::stable_sort(runs.begin(), runs.end(), [](const Run& a, const Run& b) { return a.w > b.w; });
+  int cum = 0;
+  for (size_t r = 0; r < runs.size(); ++r) {
+    o.start[r] = runs[r].start; o.cum[r] = cum; o.w[r] = runs[r].w;
+    cum += runs[r].len;
+  }
+  o.cum[runs.size()] = cum;
+  o.nruns = (int)runs.size();
+  last = Key{d.conv_H, d.conv_W, d.M, BM};
+  last_o = o;
+}
+
 // implicit-convolution launches (two-stage 64x64 variant): mode 1 = A patches (NT / NN), mode 2 = B patches (TN)
 static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStream_t s) {
   const int ve = (int)vec_epi_ok(d);
@@ -1495,9 +1615,11 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
   const bool pm = conv_pm(d) && d.conv_mode == 1, pm2 = conv_pm(d) && d.conv_mode == 2;
   if (d.conv_mode == 1 && !d.b_kmajor && nsplit == 1 && wide && d.N % 128 == 0) {
     GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 128), (int)vec_epi_ok(d)};
-    if (pm)
-      hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1, true>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, a2);
-    else
+    if (pm) {
+      GemmArgsOrd ao{a2, {}};
+      tile_order_build(d, 64, nsplit, ao.ord);
+      hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1, true>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, ao);
+    } else
       hipLaunchKernelGGL((gemm_glds_kernel<64, 128, 2, 2, 2, 3, false, false, 1, 1>), dim3(a2.tiles_m * a2.tiles_n, 1, 1), dim3(256), 0, s, a2);
     TAVSR_LAUNCH_CHECK();
     return TAVSR_OK;
@@ -1513,11 +1635,14 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
   }
   GemmArgs a{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 64), ve, zmap};
   dim3 grid(a.tiles_m * a.tiles_n, 1, nsplit);
-  if (pm && !d.b_kmajor)
-    hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, false, 1, 1, true>), grid, dim3(256), 0, s, a);
-  else if (pm)
-    hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, true, 1, 1, true>), grid, dim3(256), 0, s, a);
-  else if (d.conv_mode == 1 && !d.b_kmajor)
+  if (pm) {
+    GemmArgsOrd ao{a, {}};
+    tile_order_build(d, 64, nsplit, ao.ord);
+    if (!d.b_kmajor)
+      hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, false, 1, 1, true>), grid, dim3(256), 0, s, ao);
+    else
+      hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, true, 1, 1, true>), grid, dim3(256), 0, s, ao);
+  } else if (d.conv_mode == 1 && !d.b_kmajor)
     hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, false, 1, 1>), grid, dim3(256), 0, s, a);
   else if (d.conv_mode == 1)
     hipLaunchKernelGGL((gemm_glds_kernel<64, 64, 2, 2, 2, 5, false, true, 1, 1>), grid, dim3(256), 0, s, a);
@@ -1910,6 +2035,32 @@ extern "C" int64_t tavsr_gemm_ws(const tavsr_gemm_desc* dp) {
                    d.sA2 % 4 == 0 && d.sB1 % 4 == 0 && d.sB2 % 4 == 0;
   Plan p = d.conv_mode != 0 ? plan_conv(d, true) : plan(d, true, glds_ok(d, vec) || tail_ok(d, vec));
   return ws_floats_for(d, p.nsplit);
+}
+
+// The two entry points below exist for tests/test_gpu_conv_tileorder.py and are deliberately NOT declared in include/tavsr.h: the
+// binding resolves every prototype of the header when it loads a library, and the A/B runs load the previous commit's library
+// (TAVSR_LIB), which does not have them.  The test declares their signatures itself.
+// Host-side view of the position-major tile order (struct TileOrder), for tests: the tile (tile_m[b], tile_n[b]) that
+// workgroup b of a forward / data gradient launch over `images` H x W maps computes, with bm-row tiles and tiles_n column
+// tiles.  Returns the number of workgroups (the arrays are filled up to max_blocks), 0 when the launch keeps its old order.
+extern "C" int tavsr_conv_tile_order(int H, int W, int images, int bm, int tiles_n, int32_t* tile_m, int32_t* tile_n, int max_blocks) {
+  using namespace tavsr;
+  if (H <= 0 || W <= 0 || images <= 0 || bm <= 0 || tiles_n <= 0) return 0;
+  tavsr_gemm_desc d{};
+  d.conv_H = H; d.conv_W = W; d.M = images * H * W; d.conv_posmajor = 1;
+  TileOrder o;
+  tile_order_build(d, bm, 1, o);
+  if (o.nruns == 0) return 0;
+  const int tiles_m = cdiv(d.M, bm), nwg = tiles_m * tiles_n;
+  for (int b = 0; b < nwg && b < max_blocks; ++b) tile_order_map(o, b, tiles_m, tiles_n, tile_m[b], tile_n[b]);
+  return nwg;
+}
+
+// The same for the position-major weight gradient's order inside a K slice (dw_tile_order): tile[q] = row block * tiles_n + column tile.
+extern "C" int tavsr_conv_dw_tile_order(int H, int W, int tiles_m, int tiles_n, int32_t* tile, int max_tiles) {
+  if (H <= 0 || W <= 0 || tiles_m <= 0 || tiles_n <= 0) return 0;
+  for (int q = 0; q < tiles_m * tiles_n && q < max_tiles; ++q) tile[q] = tavsr::dw_tile_order(q, tiles_m, tiles_n, H, W);
+  return tiles_m * tiles_n;
 }
 
 #ifdef TAVSR_GEMM_TRACE

@@ -1658,10 +1658,15 @@ def conv_wflip(w2d, cout, cin):
 # few per cent of the taps are padding).  TAVSR_CONV_TAPSKIP=0: today's launches (A/B switch).
 CONV_TAPSKIP = os.environ.get("TAVSR_CONV_TAPSKIP", "1") != "0"
 CONV_TAPSKIP_MAXPOS = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS", "36"))
+# Tile order of the position-major forward / data gradient launches: tiles sorted by tap count and dealt evenly to the XCDs
+# (csrc/gemm.hip, struct TileOrder; bit-identical results).  TAVSR_CONV_TILEORDER=0: one contiguous range of tiles per XCD, as
+# before (A/B switch; bit 1 of conv_posmajor).
+CONV_TILEORDER = os.environ.get("TAVSR_CONV_TILEORDER", "1") != "0"
 
 
 def _tapskip(H, W, stride=1, taps=9, pad0=False):
-    return int(CONV_TAPSKIP and stride == 1 and taps == 9 and not pad0 and H * W <= CONV_TAPSKIP_MAXPOS)
+    on = CONV_TAPSKIP and stride == 1 and taps == 9 and not pad0 and H * W <= CONV_TAPSKIP_MAXPOS
+    return (1 if CONV_TILEORDER else 3) if on else 0
 
 
 def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None):
