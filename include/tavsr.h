@@ -121,7 +121,7 @@ typedef struct tavsr_gemm_desc {
        conv_mode 5: B is X (TN layout, a_kmajor and b_kmajor), N = 256, K = output pixels (a multiple of 32): weight gradient
                     dW[co][tap] = sum_m dY[m][co] * patch(m, tap); columns >= 245 come out 0.
      lda (mode 4) / ldb (mode 5) are ignored (pass a multiple of 4).
-     conv_posmajor (non-zero; honoured for conv_mode 1 without a_rowsum and conv_mode 2, with the 9 padded taps at stride 1;
+     conv_posmajor (non-zero; honoured for conv_mode 1 without a_rowsum and conv_mode 2, with the 9 padded taps at stride 1 - bit 3: also stride 2;
      IGNORED everywhere else - the launch is then exactly the one without it): skip the multiplications by padding.
        conv_mode 1: the tiles walk the rows position-major (virtual row r = position * images + image, positions ordered
          interior, edges, corners; only the loader's and the epilogue's addresses know - every operand stays where it is),
@@ -136,7 +136,15 @@ typedef struct tavsr_gemm_desc {
        tiles are sorted by tap count and dealt evenly to the XCDs (launches without a K split, maps whose sorted order
        fits 80 runs of m-tiles; otherwise the plain order), and the weight gradient hands out a slice's tiles heaviest tap
        first where every K slice runs on one XCD (a multiple of 8 slices; otherwise the plain order).  The same tiles either
-       way: results do not depend on the bit. */
+       way: results do not depend on the bit.
+       Bit 3 (value 8) asks for the same at stride 2 (3x3, pad 1): honoured for conv_mode 1 (forward: rows position-major over
+       the OUTPUT map, the tap set of a position from 2 * o + t - 1 lying inside the input map; bit-identical) and conv_mode 2
+       (slices of whole output images, lcm(Ho*Wo, 32) pixels) where the output map has at most 36 positions; on a larger map
+       the bit is ignored like the whole field.  Without bit 3 a stride-2 descriptor ignores the field, as before.
+       Bit 2 (value 4) keeps the weight gradient's K slices equal (A/B aid): without it, where equal slices of whole
+       lcm(H*W, 32)-pixel units leave a large part of the last round of block slots empty, the first slices are one unit
+       longer than the rest (a multiple of 8 slices; the slice count, and with it tavsr_gemm_ws, depends on the bit, and
+       so does the summation order of the weight gradient - never the forward or the data gradient). */
   int32_t conv_mode, conv_H, conv_W, conv_C;
   const float* conv_zero;
   int32_t conv_stride, conv_taps;
@@ -183,6 +191,11 @@ int tavsr_gemm_ln(const tavsr_gemm_desc* desc, const float* gamma, const float* 
  * problems one by one with tavsr_gemm. */
 int tavsr_gemm_grouped(const tavsr_gemm_desc* descs, int32_t n, tavsr_stream_t stream);
 /* tuning/bench entry: force tile configuration cfg (see kCfgs in csrc/gemm.hip; BK = 32) and a K split (<= 1: none; needs ws/sync large enough) instead of the planner's choice. */
+/* Convolution descriptors (conv_mode != 0) take no forced tile (cfg must be < 0).  nsplit is honoured for ONE kind of them only: the
+ * position-major weight gradient (conv_mode 2 with conv_posmajor honoured, bit 2 clear), where nsplit > 1 asks the planner for that
+ * many K slices of two lengths, rounded DOWN to a multiple of 8 and to at most K / lcm(Ho*Wo, 32) slices.  Where that gives fewer than
+ * 8 slices, or slices of equal length (the unit count is a multiple of the slice count), and for every other convolution descriptor,
+ * nsplit is ignored and the launch is the planner's own, exactly as tavsr_gemm's.  The workspace must hold nsplit slabs either way. */
 int tavsr_gemm_tune(const tavsr_gemm_desc* desc, int32_t cfg, int32_t nsplit, tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------

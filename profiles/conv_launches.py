@@ -1,5 +1,6 @@
 """The trunk's stride-1 3x3 convolution launches of layers 4 and 3 (3200 frames) alone, for counter runs: forward with
-conv_posmajor 0 / 3 (position-major, contiguous tile range per XCD) / 1 (sorted tile order), weight gradient with 0 / 3 / 1,
+conv_posmajor 0 / 3 (position-major, contiguous tile range per XCD) / 1 (sorted tile order), weight gradient with 0 / 3 / 1
+and 5 (bit 2: the equal K slices of before round 8; 1 and 3 take slices of two lengths where the planner gives them: layer 3),
 each launched twice; the second launch is the one summarised.
 usage: rocprofv3 --kernel-trace --pmc <counters> -d DIR -o p --output-format csv -- python3 profiles/conv_launches.py
        python profiles/conv_launches.py --summarise DIR/p_counter_collection.csv      (per launch: every counter, and hit rates)"""
@@ -13,13 +14,14 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "tailored-avsr_amd")]
 N_IMG = 3200
 LAYERS = (("layer 4", 3, 3, 512), ("layer 3", 6, 6, 256))
 FLAGS = (0, 3, 1)
+DW_FLAGS = (0, 3, 1, 5)
 
 
 def labels():
     out = []
     for name, H, W, Cc in LAYERS:
         out += [f"{name} forward NT {N_IMG * H * W}x{Cc}x{9 * Cc} posmajor={f}" for f in FLAGS]
-        out += [f"{name} wgrad TN {Cc}x{9 * Cc}x{N_IMG * H * W} posmajor={f}" for f in FLAGS]
+        out += [f"{name} wgrad TN {Cc}x{9 * Cc}x{N_IMG * H * W} posmajor={f}" for f in DW_FLAGS]
     return out
 
 
@@ -36,7 +38,7 @@ def run():
         for f in FLAGS:
             for _ in range(2):
                 ops.gemm(M, Cc, K, x, Cc, w, K, z, Cc, conv=(1, H, W, Cc, 1, 9, f))
-        for f in FLAGS:
+        for f in DW_FLAGS:
             for _ in range(2):
                 ops.gemm(Cc, K, M, dz, Cc, x, Cc, dw, K, a_kmajor=True, b_kmajor=True, conv=(2, H, W, Cc, 1, 9, f))
         torch.cuda.synchronize()

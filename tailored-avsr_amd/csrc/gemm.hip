@@ -44,6 +44,7 @@ struct GemmArgs {
   int tiles_m, tiles_n;
   int vec_epi;    // LDS-DMA kernels: epilogue through LDS with 16-byte row accesses (finish_tile_vec)
   int zmap;       // split-K convolution weight gradients: all tiles of a K slice on one XCD (see gemm_glds_kernel)
+  int n_big, kunit;   // position-major weight gradient, two slice lengths (plan_conv): slices z < n_big hold kchunk + kunit
 };
 
 // Fixed-order sum of the split-K slabs + the fused epilogue (same math as the in-kernel one); one thread per
@@ -208,12 +209,15 @@ __device__ __forceinline__ void read_frag(const float* __restrict__ s, int row, 
   }
 }
 
-// Position-major virtual rows of an implicit 3x3 / stride 1 / pad 1 convolution (tavsr_gemm_desc.conv_posmajor): virtual row
-// r = v * n + image, where v counts the H x W pixel positions interior first (9 taps inside the image), then the edges (6), then
-// the corners (4) - the tiles with the most K-steps are dispatched first.  A tile whose rows share one position (uni) maps its
-// rows without a division.
+// Position-major virtual rows of an implicit 3x3 / pad 1 convolution (tavsr_gemm_desc.conv_posmajor): virtual row
+// r = v * n + image, where v counts the H x W pixel positions of the OUTPUT map interior first (at stride 1: 9 taps inside the
+// image), then the edges (6), then the corners (4).  A tile whose rows share one position (uni) maps its rows without a division.
+// Stride st = 2: output position (y, x) is centred on input pixel (2 y, 2 x) of the HI x WI input map, so the first row / column
+// always loses its upper / left taps and the last one its lower / right taps only where the input size is odd (11 -> 6: both
+// borders, 6 -> 3: one); the classes above are then no tap classes, and the launch's order comes from struct TileOrder alone.
 struct PosMajor {
-  int n, H, W;          // images, map
+  int n, H, W;          // images, (output) map
+  int st, HI, WI;       // stride, input map (stride 1: H, W)
   int uni, base, rp;    // the tile lies on ONE position: its virtual rows start at base = v * n, rp = y * W + x
   __host__ __device__ __forceinline__ void pos(int v, int& y, int& x) const {
     const int Hi = H > 2 ? H - 2 : 0, Wi = W > 2 ? W - 2 : 0, Hb = H - Hi, Wb = W - Wi;       // interior / border coordinates
@@ -231,7 +235,7 @@ struct PosMajor {
     uint32_t mk = 0;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap)
-      mk |= (uint32_t)((unsigned)(y + tap / 3 - 1) < (unsigned)H && (unsigned)(x + tap % 3 - 1) < (unsigned)W) << tap;
+      mk |= (uint32_t)((unsigned)(st * y + tap / 3 - 1) < (unsigned)HI && (unsigned)(st * x + tap % 3 - 1) < (unsigned)WI) << tap;
     return mk;
   }
   __device__ __forceinline__ int row(int r) const {                   // the real row (image * H * W + y * W + x) of virtual row r
@@ -288,6 +292,9 @@ __host__ __device__ inline void tile_order_map(const TileOrder& o, int b, int ti
 // blocks.  Same tiles, same K order inside each: bit-identical.  Applied where a slice's tiles share an XCD (zmap: a multiple of 8
 // slices) and the column tiles are whole taps (conv_C % 64 == 0, which the launch requires, so tiles_n = 9 channel blocks; any
 // other tiles_n keeps the plain order, and a tiles_n % 9 == 0 that is not whole taps would still be a permutation of the tiles).
+// (Stride 2, bit 3: the launch passes the INPUT map, and the rank by (H - |dy|)(W - |dx|) is then not the tap's cost on the output
+// map - on 6 -> 3 the taps with dy = +1 or dx = +1 lose no position.  Still a permutation of the same tiles, so results do not
+// change, but "heaviest first" does not hold there; the stride-2 weight gradient ships switched off, ops.CONV_TAPSKIP_STRIDE2_DW.)
 __host__ __device__ inline int dw_tile_order(int q, int tiles_m, int tiles_n, int H, int W) {
   if (tiles_n % 9 != 0) return q;
   const int tpt = tiles_n / 9, per = tiles_m * tpt;
@@ -296,6 +303,24 @@ __host__ __device__ inline int dw_tile_order(int q, int tiles_m, int tiles_n, in
   const unsigned long long taps = (H - 1) * W >= H * (W - 1) ? 0x862053714ull : 0x862071534ull;
   const int tap = (int)((taps >> (4 * rank)) & 15);
   return (rem / tpt) * tiles_n + tap * tpt + rem % tpt;
+}
+
+// Two slice lengths (plan_conv): the j-th workgroup of an XCD that holds ns slices of tiles_m * tiles_n tiles each.  A tile
+// costs (positions at which its tap is inside the map) x (slice length), and the XCD's longer slices are its first ones (slice
+// z runs on XCD z % 8, the first n_big slices are the long ones), so handing out tap rank by tap rank, each rank for the
+// slices in turn, is the order of falling cost: long centre, short centre, long edges, short edges, ...  (6x6 map, 13 and 12
+// units on 96 block slots: 64.3 units of makespan against 67.5 slice by slice and a mean of 62.7; arithmetic.)  zs = the XCD's
+// zs-th slice, q = the tile's place in dw_tile_order's order inside it; a bijection of [0, ns * tiles).  Any tiles_n that
+// dw_tile_order leaves alone keeps the slices one after the other.
+__host__ __device__ inline void dw_xcd_order(int j, int tiles_m, int tiles_n, int ns, int& zs, int& q) {
+  const int tiles = tiles_m * tiles_n;
+  zs = j / tiles;
+  q = j - zs * tiles;
+  if (tiles_n % 9 != 0) return;
+  const int per = tiles_m * (tiles_n / 9);            // a slice's tiles of one tap
+  const int rank = j / (ns * per), rem = j - rank * (ns * per);
+  zs = rem / per;
+  q = rank * per + rem - zs * per;
 }
 
 // Common tail of both kernels: lane pairs complete the row sums, then either the split-K slab store or the fused
@@ -731,10 +756,11 @@ __device__ unsigned int g_trace_n;
 // operand is fetched with the GEMM's ordinary 16-byte LDS-DMA (two per thread and K-step instead of eight 4-byte gathers; the
 // source is only 8-byte aligned, which gfx950's global_load_lds takes) and no validity test is left:
 //   6: A(m, k) = xp[clip][t + kt][2 ho + kh][2 wo + kw];   7: B(k = pixel, n = tap) likewise (weight gradient).
-// PM (CONV 1, 3x3 / stride 1 / pad 1 only): position-major virtual rows, K-steps of all-padding taps skipped (struct PosMajor).
+// PM (CONV 1 / CONV 2, 3x3 / pad 1, stride 1 or 2 - conv_pm): position-major virtual rows (CONV 1) or pixel walk (CONV 2), K-steps of
+// all-padding taps skipped (struct PosMajor).
 template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
 __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, int nsplit, int tiles_n, int bid, bool vec_epi,
-                                          int zidx) {
+                                          int zidx, int n_big = 0, int kunit = 0) {
   constexpr int BK = 32, NG = BK / 8;
   static_assert(NG % KW == 0, "k-groups must divide over the wave sets");
   constexpr int NT = WM * WN * KW * 64;
@@ -782,8 +808,9 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
     bpre[j] = (d.bias && nsplit == 1 && n < d.N) ? d.bias[n] : 0.f;
   }
 
-  const int kbeg = zidx * kchunk;
-  const int kend = min(d.K, kbeg + kchunk);
+  // (two slice lengths: the first n_big slices are kunit longer, plan_conv; n_big = 0 everywhere else)
+  const int kbeg = zidx * kchunk + min(zidx, n_big) * kunit;
+  const int kend = min(d.K, kbeg + kchunk + (zidx < n_big ? kunit : 0));
   int nk = CONV == 3 ? (kend - kbeg + BK - 1) / BK : (kend - kbeg) / BK;     // whole K-steps (host guarantees it); CONV 3: K tail
   const int64_t kstepA = AK ? (int64_t)BK * d.lda : BK;
   const int64_t kstepB = BKM ? (int64_t)BK * d.ldb : BK;
@@ -805,14 +832,15 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   uint32_t pm_taps = 0;
   int pm_tap = 0, pm_cb = 0;
   if (PM && CONV == 1) {
-    pm.H = d.conv_H; pm.W = d.conv_W;
-    pm.n = d.M / (d.conv_H * d.conv_W);
+    pm.H = cHo; pm.W = cWo;                           // the rows are output pixels (stride 1: the input map)
+    pm.st = cs; pm.HI = d.conv_H; pm.WI = d.conv_W;
+    pm.n = d.M / (cHo * cWo);
     const int vlo = m0 / pm.n, vhi = min(m0 + BM - 1, d.M - 1) / pm.n;
     for (int v = vlo; v <= vhi; ++v) {
       int y, x;
       pm.pos(v, y, x);
       pm_taps |= pm.taps(y, x);
-      pm.rp = y * d.conv_W + x;
+      pm.rp = y * cWo + x;
     }
     pm.uni = vlo == vhi;
     pm.base = vlo * pm.n;
@@ -834,13 +862,13 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
       const int r = min(m0 + row, d.M - 1);
       int y, x, img;
       if (pm.uni) {
-        y = pm.rp / d.conv_W; x = pm.rp - y * d.conv_W; img = r - pm.base;
+        y = pm.rp / cWo; x = pm.rp - y * cWo; img = r - pm.base;
       } else {
         const int v = r / pm.n;
         pm.pos(v, y, x);
         img = r - v * pm.n;
       }
-      offA[i] = ((int64_t)img * (d.conv_H * d.conv_W) + y * d.conv_W + x) * d.lda + ((q & 7) ^ ((row >> 1) & 7)) * 4;
+      offA[i] = ((int64_t)img * (d.conv_H * d.conv_W) + cs * y * d.conv_W + cs * x) * d.lda + ((q & 7) ^ ((row >> 1) & 7)) * 4;
       cmask[i] = pm.taps(y, x);
     }
   } else if (CONV == 1) {
@@ -965,26 +993,31 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   // consecutive k' share their position (or straddle a few) and the steps at whose positions this tile's tap is padding are
   // passed over: neither fetched nor multiplied.  Every pixel of the slice is still summed exactly once for every tap.
   // (p2_v = y * W + x, p2_img): where the next candidate step starts - workgroup-uniform.
+  // Stride 2: the positions are those of the cHo x cWo OUTPUT map (K counts output pixels), position (y, x) reads input pixel
+  // (2 y + dy, 2 x + dx) of the conv_H x conv_W input map.
   int p2_n = 1, p2_i0 = 0, p2_v = 0, p2_img = 0, p2_x = 0, p2_y = 0;
   auto p2_ok = [&](int y, int x) {
-    return (unsigned)(y + c2_dy) < (unsigned)d.conv_H && (unsigned)(x + c2_dx) < (unsigned)d.conv_W;
+    return (unsigned)(cs * y + c2_dy) < (unsigned)d.conv_H && (unsigned)(cs * x + c2_dx) < (unsigned)d.conv_W;
   };
   auto p2_advance = [&]() {
     p2_img += BK;
     while (p2_img >= p2_n) {
       p2_img -= p2_n;
       ++p2_v;
-      if (++p2_x == d.conv_W) { p2_x = 0; ++p2_y; }
+      if (++p2_x == cWo) { p2_x = 0; ++p2_y; }
     }
   };
   if (PM && CONV == 2) {
-    const int P = d.conv_H * d.conv_W;
+    const int P = cHo * cWo;
     p2_i0 = kbeg / P;
     p2_n = (kend - kbeg) / P;
 #pragma unroll
     for (int i = 0; i < LA::NR; ++i) offA[i] -= (int64_t)((i * NT + tid) / (BM / 4)) * d.lda;      // the row part; k is gathered
     if (p2_n % BK == 0) {       // every step lies on one position
-      nk = (p2_n / BK) * max(d.conv_H - abs(c2_dy), 0) * max(d.conv_W - abs(c2_dx), 0);
+      int ny = 0, nx = 0;       // rows / columns of positions at which the tap is inside the image
+      for (int y = 0; y < cHo; ++y) ny += (unsigned)(cs * y + c2_dy) < (unsigned)d.conv_H;
+      for (int x = 0; x < cWo; ++x) nx += (unsigned)(cs * x + c2_dx) < (unsigned)d.conv_W;
+      nk = (p2_n / BK) * ny * nx;
     } else {                    // the steps that touch a position where the tap is inside the image
       nk = 0;
       int prev = 0, y = 0, x = 0;
@@ -993,7 +1026,7 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
           const int s_lo = max(v * p2_n / BK, prev), s_hi = ((v + 1) * p2_n - 1) / BK + 1;
           if (s_hi > s_lo) { nk += s_hi - s_lo; prev = s_hi; }
         }
-        if (++x == d.conv_W) { x = 0; ++y; }
+        if (++x == cWo) { x = 0; ++y; }
       }
     }
   }
@@ -1021,33 +1054,36 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
           any |= p2_ok(y, x);
           if (end <= p2_n) break;
           end -= p2_n;
-          if (++x == d.conv_W) { x = 0; ++y; }
+          if (++x == cWo) { x = 0; ++y; }
         }
         if (any) break;
         p2_advance();
       }
-      const int P = d.conv_H * d.conv_W;
-      auto locate = [&](int kl, int& y, int& x) {        // pixel of the step's k row kl, and its position
-        int img = p2_img + kl, v = p2_v;
+      const int P = cHo * cWo;
+      auto locate = [&](int kl, int& y, int& x, int& img) {        // output pixel of the step's k row kl, its position and image
+        int v = p2_v;
+        img = p2_img + kl;
         y = p2_y; x = p2_x;
         while (img >= p2_n) {
           img -= p2_n;
           ++v;
-          if (++x == d.conv_W) { x = 0; ++y; }
+          if (++x == cWo) { x = 0; ++y; }
         }
-        return (int64_t)(p2_i0 + img) * P + v;
+        img += p2_i0;
+        return (int64_t)img * P + v;
       };
 #pragma unroll
       for (int i = 0; i < LA::NR; ++i) {
-        int y, x;
-        const int64_t pix = locate((i * NT + tid) / (BM / 4), y, x);
+        int y, x, img;
+        const int64_t pix = locate((i * NT + tid) / (BM / 4), y, x, img);
         __builtin_amdgcn_global_load_lds((glb_float*)(A + pix * d.lda + offA[i]), (lds_float*)(smem + st * STAGE + (i * NT + wave * 64) * 4), 16, 0, 0);
       }
 #pragma unroll
       for (int i = 0; i < LB::NR; ++i) {
         const int r = (((i * NT + tid) % (BN / 4)) * 4);
-        int y, x;
-        const int64_t pix = locate((i * NT + tid) / (BN / 4), y, x);
+        int y, x, img;
+        locate((i * NT + tid) / (BN / 4), y, x, img);
+        const int64_t pix = ((int64_t)img * d.conv_H + cs * y) * d.conv_W + cs * x;      // the position's input pixel (stride 1: the same pixel)
         const float* src = p2_ok(y, x) ? B + (pix + c2_tapoff) * d.conv_C + c2_cb + r : d.conv_zero;
         __builtin_amdgcn_global_load_lds((glb_float*)src, (lds_float*)(smem + st * STAGE + ASZ + (i * NT + wave * 64) * 4), 16, 0, 0);
       }
@@ -1346,13 +1382,18 @@ void gemm_glds_kernel(const std::conditional_t<PM && CONV == 1, GemmArgsOrd, Gem
     // others.  Launch l = x + tiles * z runs on XCD l % 8 as that XCD's (l / 8)-th block: slice (l % 8) + 8 * ((l / 8) /
     // tiles), tile (l / 8) % tiles - a bijection when the number of slices is a multiple of 8 (host).
     const int tiles = gridDim.x, l = blockIdx.x + tiles * blockIdx.z, j = l >> 3;
-    zidx = (l & 7) + 8 * (j / tiles);
+    int zs = j / tiles;
     bid = j % tiles;
     if constexpr (PM && CONV == 2) {
-      if (!(args.d.conv_posmajor & 2)) bid = dw_tile_order(bid, args.tiles_m, args.tiles_n, args.d.conv_H, args.d.conv_W);
+      if (!(args.d.conv_posmajor & 2)) {
+        if (args.n_big > 0) dw_xcd_order(j, args.tiles_m, args.tiles_n, args.nsplit >> 3, zs, bid);
+        bid = dw_tile_order(bid, args.tiles_m, args.tiles_n, args.d.conv_H, args.d.conv_W);
+      }
     }
+    zidx = (l & 7) + 8 * zs;
   }
-  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx);
+  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx,
+                                                      args.n_big, args.kunit);
 }
 
 // Grouped launch: up to kMaxGroup independent problems of one layout share ONE grid (tile ranges by prefix sums).
@@ -1514,26 +1555,43 @@ static int launch_glds(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
   return rc ? rc : launch_epilogue(a, s);
 }
 
-// tavsr_gemm_desc.conv_posmajor applies: 3x3 / stride 1 / pad 1, forward / data gradient (no row sums there) or weight gradient
+// output map of a padded 3x3 convolution descriptor
+static int conv_ho(const tavsr_gemm_desc& d) { return (d.conv_H - 1) / std::max(d.conv_stride, 1) + 1; }
+static int conv_wo(const tavsr_gemm_desc& d) { return (d.conv_W - 1) / std::max(d.conv_stride, 1) + 1; }
+
+// tavsr_gemm_desc.conv_posmajor applies: 3x3 / pad 1, forward / data gradient (no row sums there) or weight gradient, at stride 1,
+// or at stride 2 where bit 3 asks for it and the output map has at most kPmStride2MaxPos positions (trunk layers 3 and 4 open
+// with 11 -> 6 and 6 -> 3: 0.79 of the taps inside the image; at 22 -> 11 it is 0.94 and the position bookkeeping costs more
+// than the skipped K-steps give, as it did on the 11x11 map at stride 1 - such a descriptor gets the launch without the flag)
+constexpr int kPmStride2MaxPos = 36;
 static bool conv_pm(const tavsr_gemm_desc& d) {
-  return d.conv_posmajor && (d.conv_mode == 1 || d.conv_mode == 2) && d.conv_stride <= 1 && (d.conv_taps == 0 || d.conv_taps == 9) &&
+  const bool stride_ok = d.conv_stride <= 1 || (d.conv_stride == 2 && (d.conv_posmajor & 8) && conv_ho(d) * conv_wo(d) <= kPmStride2MaxPos);
+  return d.conv_posmajor && (d.conv_mode == 1 || d.conv_mode == 2) && stride_ok && (d.conv_taps == 0 || d.conv_taps == 9) &&
          (d.conv_mode == 2 || !d.a_rowsum);
 }
 
 // The sorted tile order of a position-major forward / data gradient launch with BM-row tiles (struct TileOrder).  nruns stays 0,
 // and the launch keeps its old order, for a K split (the grid's z axis moves the workgroups' XCDs), where conv_posmajor's bit 1
-// asks for it (A/B aid: ops.CONV_TILEORDER) and on a map with more runs than the table holds.
+// asks for it (A/B aid: ops.CONV_TILEORDER) and on a map with more runs than the table holds.  The bound is kOrdRuns = 80 runs
+// of consecutive m-tiles with one tap count, counted BEFORE sorting.  Tiles that sit on one position each give one run per
+// class of positions (an 11x11 map at 3200 frames: 3 runs).  Where tiles straddle positions the count changes from tile to
+// tile along the left / right border, whose positions alternate: a tile over both sides has 9 taps, its neighbour on one
+// side 6.  An 11x11 map stays within the bound at every image count from 1 to 200; tall maps do not (60x3 from 84 images,
+// 22x22 at 119 - 129 images), and then the whole launch keeps the plain order - the same tiles with the same K-steps,
+// bit-identical - rather than a truncated table.
 static void tile_order_build(const tavsr_gemm_desc& d, int BM, int nsplit, TileOrder& o) {
   o.nruns = 0;
-  const int P = d.conv_H * d.conv_W;
+  const int cs = std::max(d.conv_stride, 1);
+  const int P = conv_ho(d) * conv_wo(d);            // the rows are output pixels
   if (nsplit != 1 || (d.conv_posmajor & 2) || P <= 0 || d.M < P) return;
-  // the order depends on (H, W, M, BM) alone and a step repeats a handful of them: keep the last one built per thread
-  struct Key { int H, W, M, BM; };
-  static thread_local Key last{0, 0, 0, 0};
+  // the order depends on (H, W, stride, M, BM) alone and a step repeats a handful of them: keep the last one built per thread
+  struct Key { int H, W, cs, M, BM; };
+  static thread_local Key last{0, 0, 0, 0, 0};
   static thread_local TileOrder last_o;
-  if (last.H == d.conv_H && last.W == d.conv_W && last.M == d.M && last.BM == BM) { o = last_o; return; }
+  if (last.H == d.conv_H && last.W == d.conv_W && last.cs == cs && last.M == d.M && last.BM == BM) { o = last_o; return; }
   PosMajor pm{};
-  pm.H = d.conv_H; pm.W = d.conv_W; pm.n = d.M / P;
+  pm.H = conv_ho(d); pm.W = conv_wo(d); pm.n = d.M / P;
+  pm.st = cs; pm.HI = d.conv_H; pm.WI = d.conv_W;
   std::vector<uint32_t> tp(P);
   for (int v = 0; v < P; ++v) {
     int y, x;
@@ -1561,12 +1619,12 @@ static void tile_order_build(const tavsr_gemm_desc& d, int BM, int nsplit, TileO
   }
   o.cum[runs.size()] = cum;
   o.nruns = (int)runs.size();
-  last = Key{d.conv_H, d.conv_W, d.M, BM};
+  last = Key{d.conv_H, d.conv_W, cs, d.M, BM};
   last_o = o;
 }
 
 // implicit-convolution launches (two-stage 64x64 variant): mode 1 = A patches (NT / NN), mode 2 = B patches (TN)
-static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStream_t s) {
+static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStream_t s, int n_big = 0, int kunit = 0) {
   const int ve = (int)vec_epi_ok(d);
   // Wider tiles where the shape allows - the gathered patch operand is the expensive one to load:
   //   forward / data gradient: a 64x128 tile reads the image rows once for two column tiles of weights (Cout % 128 == 0):
@@ -1610,8 +1668,9 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
     TAVSR_LAUNCH_CHECK();
     return launch_epilogue(a4, s);
   }
-  // conv_posmajor: honoured for the 9 padded taps at stride 1 (ignored elsewhere, include/tavsr.h): same tiles; forward / data
-  // gradient keep their K split, the weight gradient's slices are whole images (plan_conv)
+  // conv_posmajor: honoured for the 9 padded taps at stride 1, and at stride 2 on small maps where bit 3 asks (conv_pm; ignored
+  // elsewhere, include/tavsr.h): same tiles; forward / data gradient keep their K split, the weight gradient's slices are
+  // whole images (plan_conv)
   const bool pm = conv_pm(d) && d.conv_mode == 1, pm2 = conv_pm(d) && d.conv_mode == 2;
   if (d.conv_mode == 1 && !d.b_kmajor && nsplit == 1 && wide && d.N % 128 == 0) {
     GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 128), (int)vec_epi_ok(d)};
@@ -1625,7 +1684,7 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
     return TAVSR_OK;
   }
   if (d.conv_mode == 2 && dw_wide && d.M % 128 == 0) {     // weight gradient: 128 output channels share one patch tile
-    GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 128), cdiv(d.N, 64), (int)vec_epi_ok(d), zmap};
+    GemmArgs a2{d, kchunk, nsplit, cdiv(d.M, 128), cdiv(d.N, 64), (int)vec_epi_ok(d), zmap, pm2 ? n_big : 0, pm2 ? kunit : 0};
     if (pm2)
       hipLaunchKernelGGL((gemm_glds_kernel<128, 64, 2, 2, 2, 3, true, true, 1, 2, true>), dim3(a2.tiles_m * a2.tiles_n, 1, nsplit), dim3(256), 0, s, a2);
     else
@@ -1633,7 +1692,7 @@ static int launch_conv(const tavsr_gemm_desc& d, int nsplit, int kchunk, hipStre
     TAVSR_LAUNCH_CHECK();
     return launch_epilogue(a2, s);
   }
-  GemmArgs a{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 64), ve, zmap};
+  GemmArgs a{d, kchunk, nsplit, cdiv(d.M, 64), cdiv(d.N, 64), ve, zmap, pm2 ? n_big : 0, pm2 ? kunit : 0};
   dim3 grid(a.tiles_m * a.tiles_n, 1, nsplit);
   if (pm) {
     GemmArgsOrd ao{a, {}};
@@ -1698,6 +1757,7 @@ static int launch(int cfg, const tavsr_gemm_desc& d, bool vec, int nsplit, int k
 
 struct Plan {
   int cfg, nsplit, kchunk;
+  int n_big = 0, kunit = 0;     // two slice lengths (plan_conv): the first n_big slices hold kchunk + kunit
 };
 
 // Can the LDS-DMA kernel take this problem?  (unpredicated 16-byte loads: aligned operands, whole K-steps per
@@ -1744,7 +1804,7 @@ static Plan plan(const tavsr_gemm_desc& d, bool allow_split, bool fast) {
 
 // plan of an implicit-convolution launch: the weight gradient (mode 2) has an enormous K = frames*H*W and few tiles, so K
 // is split until all five block slots of every CU are filled (the slabs stay tiny)
-static Plan plan_conv(const tavsr_gemm_desc& d, bool can_split) {
+static Plan plan_conv(const tavsr_gemm_desc& d, bool can_split, int force_split = 0) {
   Plan pc = plan(d, can_split, true);
   if ((d.conv_mode == 2 || d.conv_mode == 5 || d.conv_mode == 7) && can_split) {
     constexpr int dw_wide = 1;
@@ -1757,7 +1817,7 @@ static Plan plan_conv(const tavsr_gemm_desc& d, bool can_split) {
     // tap's tile costs the same in every slice and the XCDs stay balanced): slices of lcm(H * W, 32) pixels
     int unit = 32;
     if (conv_pm(d)) {
-      const int P = d.conv_H * d.conv_W;
+      const int P = conv_ho(d) * conv_wo(d);         // K counts output pixels
       int g = P, b = 32;
       while (b) { const int t = g % b; g = b; b = t; }
       unit = P / g * 32;
@@ -1776,6 +1836,26 @@ static Plan plan_conv(const tavsr_gemm_desc& d, bool can_split) {
         const int kc = cdiv(cdiv(d.K, w8), unit) * unit;
         if (cdiv(d.K, kc) % 8 == 0) { pc.kchunk = kc; pc.nsplit = cdiv(d.K, kc); break; }
         if (w8 < pc.nsplit / 2) break;
+      }
+    }
+    // Two slice lengths (position-major weight gradient; conv_posmajor's bit 2 keeps the equal slices, A/B aid
+    // ops.CONV_DW_UNEVEN).  K is a whole number U of units, and where no multiple of 8 divides U well the equal slices above
+    // leave block slots empty: layer 3 at 3200 frames is U = 400, 24 slices of 17 units (the last of 9) = 1728 blocks = 2.25
+    // rounds of the 768 slots, and the launch lasts 3 rounds of 17-unit tiles.  With w slices, w a multiple of 8, the first
+    // U % w of them one unit longer than the rest, the target is met exactly (32 slices, 16 of 13 and 16 of 12 units: 2304
+    // blocks) and every XCD gets the same mix of long and short slices to within one (slice z runs on XCD z % 8).  Taken only
+    // where the equal plan misses the target by more than a quarter of a round of block slots and this one does not; an
+    // equal plan that fills its rounds (layer 4 at 8 slices) is left alone.  force_split (tavsr_gemm_tune; tests) asks for
+    // that many slices, rounded down to a multiple of 8, whatever the targets say.
+    if (conv_pm(d) && d.conv_mode == 2 && !(d.conv_posmajor & 4) && d.K % unit == 0) {
+      const long U = d.K / unit, round4 = (wide ? 768 : 1280) / 4;
+      const long w = std::min<long>(force_split > 0 ? force_split : want, U) / 8 * 8;
+      const bool missed = target - (long)pc.nsplit * tiles > round4, hits = target - w * tiles <= round4;
+      if (w >= 8 && U % w != 0 && (force_split > 0 || (missed && hits))) {
+        pc.nsplit = (int)w;
+        pc.kchunk = (int)(U / w) * unit;
+        pc.n_big = (int)(U % w);
+        pc.kunit = unit;
       }
     }
   }
@@ -1917,9 +1997,9 @@ static int run(const tavsr_gemm_desc* dp, int force_cfg, int force_split, hipStr
     else
       TAVSR_REQUIRE(d.a_kmajor && d.b_kmajor && d.N == taps * d.conv_C && d.conv_C % 64 == 0 && d.ldb == d.conv_C,
                     TAVSR_EUNSUPPORTED, "tavsr_gemm: conv mode 2 needs the TN layout, N = taps * C, C %% 64 == 0");
-    Plan pc = plan_conv(d, can_split);
+    Plan pc = plan_conv(d, can_split, force_split);
     if (pc.nsplit > 1 && d.ws_floats < ws_floats_for(d, pc.nsplit)) pc = plan(d, false, true);
-    return launch_conv(d, pc.nsplit, pc.kchunk, s);
+    return launch_conv(d, pc.nsplit, pc.kchunk, s, pc.n_big, pc.kunit);
   }
   const bool tail = !fast && force_cfg < 0 && tail_ok(d, vec);
   if (d.drop_p > 0.f) {
@@ -2061,6 +2141,34 @@ extern "C" int tavsr_conv_dw_tile_order(int H, int W, int tiles_m, int tiles_n, 
   if (H <= 0 || W <= 0 || tiles_m <= 0 || tiles_n <= 0) return 0;
   for (int q = 0; q < tiles_m * tiles_n && q < max_tiles; ++q) tile[q] = tavsr::dw_tile_order(q, tiles_m, tiles_n, H, W);
   return tiles_m * tiles_n;
+}
+
+// The K split the planner gives the weight gradient of a 3x3 / stride 1 / pad 1 convolution over `images` H x W maps (Cin ->
+// Cout channels) with conv_posmajor = posmajor, as tavsr_gemm would launch it with a workspace large enough: returns the number
+// of slices, out = {kchunk, n_big, kunit} (slices z < n_big hold kchunk + kunit pixels, the others kchunk; the last one
+// whatever is left of K).  Like the two above: for tests, not in the header.
+extern "C" int tavsr_conv_dw_plan(int H, int W, int cin, int cout, int images, int posmajor, int force_split, int32_t* out) {
+  using namespace tavsr;
+  if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || images <= 0 || !out) return 0;
+  tavsr_gemm_desc d{};
+  d.conv_mode = 2; d.conv_H = H; d.conv_W = W; d.conv_C = cin; d.conv_stride = 1; d.conv_taps = 9; d.conv_posmajor = posmajor;
+  d.M = cout; d.N = 9 * cin; d.K = images * H * W; d.a_kmajor = d.b_kmajor = 1; d.nb1 = d.nb2 = 1;
+  const Plan p = plan_conv(d, true, force_split);
+  out[0] = p.kchunk; out[1] = p.n_big; out[2] = p.kunit;
+  return p.nsplit;
+}
+
+// ... and the order in which an XCD with ns slices of two lengths hands out their tiles (dw_xcd_order, then dw_tile_order):
+// slice[j] = the XCD's slice of its j-th workgroup, tile[j] = row block * tiles_n + column tile.
+extern "C" int tavsr_conv_dw_xcd_order(int H, int W, int tiles_m, int tiles_n, int ns, int32_t* slice, int32_t* tile, int max_tiles) {
+  if (H <= 0 || W <= 0 || tiles_m <= 0 || tiles_n <= 0 || ns <= 0) return 0;
+  for (int j = 0; j < ns * tiles_m * tiles_n && j < max_tiles; ++j) {
+    int zs, q;
+    tavsr::dw_xcd_order(j, tiles_m, tiles_n, ns, zs, q);
+    slice[j] = zs;
+    tile[j] = tavsr::dw_tile_order(q, tiles_m, tiles_n, H, W);
+  }
+  return ns * tiles_m * tiles_n;
 }
 
 #ifdef TAVSR_GEMM_TRACE

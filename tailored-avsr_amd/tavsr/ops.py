@@ -1653,20 +1653,53 @@ def conv_wflip(w2d, cout, cin):
 
 # Padding taps of the stride-1 3x3 / pad 1 convolutions (tavsr_gemm_desc.conv_posmajor): forward and data gradient walk their
 # rows position-major and skip the K-steps of the taps that are padding for a whole tile (bit-identical results); the weight
-# gradient walks the pixels of a K slice position-major and skips the steps where its tile's tap is padding.  Applied to maps
-# of at most CONV_TAPSKIP_MAXPOS positions (trunk layers 3 and 4: 6x6 and 3x3; on the 11x11 and 22x22 maps of layers 2 and 1 a
-# few per cent of the taps are padding).  TAVSR_CONV_TAPSKIP=0: today's launches (A/B switch).
+# gradient walks the pixels of a K slice position-major and skips the steps where its tile's tap is padding.  Forward and data
+# gradient: maps of at most CONV_TAPSKIP_MAXPOS positions (trunk layers 2 - 4: 11x11, 6x6, 3x3; the 11x11 map lost under the
+# unbalanced tile order of round 6 and gains 10 % of its launches under CONV_TILEORDER; on layer 1's 22x22 map 6 % of the taps
+# are padding).  TAVSR_CONV_TAPSKIP=0: the launches without the flag (A/B switch).
 CONV_TAPSKIP = os.environ.get("TAVSR_CONV_TAPSKIP", "1") != "0"
-CONV_TAPSKIP_MAXPOS = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS", "36"))
+CONV_TAPSKIP_MAXPOS = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS", "121"))
 # Tile order of the position-major forward / data gradient launches: tiles sorted by tap count and dealt evenly to the XCDs
 # (csrc/gemm.hip, struct TileOrder; bit-identical results).  TAVSR_CONV_TILEORDER=0: one contiguous range of tiles per XCD, as
 # before (A/B switch; bit 1 of conv_posmajor).
 CONV_TILEORDER = os.environ.get("TAVSR_CONV_TILEORDER", "1") != "0"
+# The weight gradient has a gate of its own: its position-major walk costs bookkeeping per K-step that the forward does not
+# pay, so a map can gain in one direction and lose in the other: the 11x11 map's weight gradient is 4 % SLOWER with the skip
+# (profiles/r08_notes.md has the per-shape rows behind both gates) and stays outside.
+CONV_TAPSKIP_MAXPOS_DW = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS_DW", "36"))
+# K slices of two lengths for the position-major weight gradient where equal slices leave block slots empty (csrc/gemm.hip,
+# plan_conv: trunk layer 3 at 3200 frames, 32 slices instead of 24; another summation order).  TAVSR_CONV_DW_UNEVEN=0: equal
+# slices, as before (A/B switch; bit 2 of conv_posmajor).
+CONV_DW_UNEVEN = os.environ.get("TAVSR_CONV_DW_UNEVEN", "1") != "0"
 
 
-def _tapskip(H, W, stride=1, taps=9, pad0=False):
-    on = CONV_TAPSKIP and stride == 1 and taps == 9 and not pad0 and H * W <= CONV_TAPSKIP_MAXPOS
-    return (1 if CONV_TILEORDER else 3) if on else 0
+# The stride-2 3x3 / pad 1 convolutions that open trunk layers 3 and 4 (11 -> 6 and 6 -> 3: 0.79 of the taps inside the image;
+# bit 3 of conv_posmajor, honoured up to 6x6 output positions, so layer 2's 22 -> 11 keeps its launch): forward, bit-identical,
+# and weight gradient, another summation order, each with its own switch (TAVSR_CONV_TAPSKIP_STRIDE2 / _STRIDE2_DW = 0 / 1).
+# The forward gains 21 % of its two launches and is on; the weight gradient gained 7 % on one launch and lost 4 % on the other,
+# inside the call's noise in sum, and ships off (profiles/r08_notes.md).
+CONV_TAPSKIP_STRIDE2 = os.environ.get("TAVSR_CONV_TAPSKIP_STRIDE2", "1") != "0"
+CONV_TAPSKIP_STRIDE2_DW = os.environ.get("TAVSR_CONV_TAPSKIP_STRIDE2_DW", "0") != "0"
+CONV_TAPSKIP_STRIDE2_MAXPOS = 36
+
+
+def _tapskip_bits():
+    return 1 | (0 if CONV_TILEORDER else 2) | (0 if CONV_DW_UNEVEN else 4)
+
+
+def _tapskip(H, W, stride=1, taps=9, pad0=False, dw=False):
+    on = CONV_TAPSKIP and stride == 1 and taps == 9 and not pad0 and H * W <= (CONV_TAPSKIP_MAXPOS_DW if dw else CONV_TAPSKIP_MAXPOS)
+    return _tapskip_bits() if on else 0
+
+
+def _tapskip2(H, W, dw=False):
+    """conv_posmajor of a stride-2 3x3 / pad 1 convolution over H x W input maps"""
+    on = CONV_TAPSKIP and (CONV_TAPSKIP_STRIDE2_DW if dw else CONV_TAPSKIP_STRIDE2)
+    return (_tapskip_bits() | 8) if on and ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) <= CONV_TAPSKIP_STRIDE2_MAXPOS else 0
+
+
+def _tapskip_any(H, W, stride, taps, pad0, dw=False):
+    return _tapskip2(H, W, dw) if stride == 2 and taps == 9 and not pad0 else _tapskip(H, W, stride, taps, pad0, dw)
 
 
 def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None):
@@ -1681,7 +1714,7 @@ def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None)
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     Mo = M // (H * W) * Ho * Wo
     z = empty(Mo, cout, like=x)
-    gemm(Mo, cout, taps * cin, x, cin, w2d, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps, _tapskip(H, W, stride, taps, pad0)),
+    gemm(Mo, cout, taps * cin, x, cin, w2d, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0)),
          bias=bias, act=act)
     return z
 
@@ -1696,15 +1729,16 @@ def conv3x3_dx(dz, wflip, H, W, res=None):
     return dx
 
 
-def conv3x3_dw(dz, x, H, W, stride=1, taps=9, pad0=False, bias_grad=False):
+def conv3x3_dw(dz, x, H, W, stride=1, taps=9, pad0=False, bias_grad=False, force=None):
     """weight gradient: dz [output pixels, Cout], x [images*H*W, Cin] -> [Cout, taps*Cin]; needs output pixels % 32 == 0.
-    ``bias_grad``: also the column sums of dz (the bias gradient) from the same launch."""
+    ``bias_grad``: also the column sums of dz (the bias gradient) from the same launch.  ``force`` = (-1, slices): ask the
+    planner for that many K slices (tavsr_gemm_tune; tests)."""
     M, cout = dz.shape
     cin = x.shape[1]
     dw = empty(cout, taps * cin, like=dz)
     gb = empty(cout, like=dz) if bias_grad else None
     gemm(cout, taps * cin, M, dz, cout, x, cin, dw, taps * cin, a_kmajor=True, b_kmajor=True,
-         conv=(2, H, W, cin, stride, 90 if pad0 else taps, _tapskip(H, W, stride, taps, pad0)), a_rowsum=gb)
+         conv=(2, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0, dw=True)), a_rowsum=gb, force=force)
     return (dw, gb) if bias_grad else dw
 
 
