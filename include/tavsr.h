@@ -926,6 +926,9 @@ int tavsr_tree_attn_step(const float* q, int64_t ldq, const float* kpool, const 
                          int32_t group, tavsr_stream_t stream);
 int tavsr_kv_append(const float* k, const float* v, int64_t ld_src, float* kpool, float* vpool, int64_t ldkv, int32_t N,
                     int32_t D, int32_t max_steps, const int32_t* step_dev, tavsr_stream_t stream);
+/* tavsr_ctc_prefix_step with cand == NULL: every token is a candidate (candidate c is token c; C must equal V) - the form of a search
+ * without pre-beam.  Its sums are the ones tavsr_ctc_beam_search computes, bit for bit: both write the recursion's one multiply-add as
+ * a fused one, where the form with a candidate list leaves the choice to the compiler, as it always did. */
 int tavsr_ctc_prefix_step(const float* logp, const int64_t* lens, const float* r_prev, const float* s_prev,
                           const int64_t* last_tok, const int64_t* cand, float* r_new, float* psi, float* psi_abs, float* eos,
                           float* eos_abs, int32_t N, int32_t K, int32_t T, int32_t V, int32_t C, int32_t out_len,
@@ -986,6 +989,30 @@ int tavsr_beam_reorder_begin(const int64_t* top_i, const float* top_s, const int
  * bits) at row *step_dev: the host rebuilds ended hypotheses from these back-pointers without reading the state back. */
 int tavsr_beam_step_begin(float* score, const int64_t* tok, int32_t* anc, int32_t ld_a, const int32_t* maxlen, int32_t N, int32_t K,
                           int32_t eos, const int32_t* step_dev, tavsr_stream_t stream);
+/* Null operands of the beam update (a search with a scorer absent, as espnet drops a scorer that is None or has weight 0:
+ * avsr_inference.py:141-153, espnet BeamSearch.__init__):
+ *   tavsr_beam_select_topk: dec == NULL - no decoder term, the row starts from w_lm * log_softmax(z_lm) + add, or from `add` alone when
+ *       z_lm is NULL too (with dec given and z_lm NULL `add` is not used: it rode in dec); psi_all == NULL - no CTC term: no pre-beam
+ *       rounds, weighted = full + score, and psi_abs_all / eos_s / eos_abs / s_prev / cand_out are ignored.  C == V selects every token
+ *       (the ctc_weight == 1 form).  One of dec / psi_all must be given.
+ *   tavsr_beam_combine / tavsr_beam_combine_topk: psi == NULL - weighted = full + score; cand, psi_abs, eos_s, eos_abs, s_prev ignored.
+ *   tavsr_beam_reorder / _begin: r_new == NULL - no CTC state to gather; cand, psi_abs, r_out and s_out are ignored.
+ * With every operand given the kernels take the code paths they had before these forms existed. */
+/* The whole CTC prefix beam search of every utterance in ONE launch: scorers {CTC prefix scorer (weight w_ctc), length bonus (add per
+ * token)}, no pre-beam - what espnet's BatchBeamSearch runs for a CTC-only recipe (avsr_inference.py:141-153, 277-304, 449-518 with
+ * decoder = None, ctc_weight = 1, no LM).  One workgroup per utterance; the beam's forward variables [K][T][2] stay in LDS (two buffers,
+ * 16 K T bytes + a few KB of 160 KiB).  logp [U][T][V] log-softmax of the CTC head, lens [U], maxlen [U] (token budget, <= lens[u]).
+ * Per token the K x V prefix scores (tavsr_ctc_prefix_step with cand == NULL, bit for bit), weighted = add + w_ctc * (psi - s_prev) +
+ * score (tavsr_beam_select_topk with dec = z_lm = NULL, C = V), the top-K (descending, lower index first among equals) and the
+ * bookkeeping of tavsr_beam_reorder_begin: hist [hist_steps][3][U * K] receives (token, extended slot, score bits) per token and slot,
+ * a hypothesis that took <eos> or whose utterance used up maxlen[u] leaves the beam.  end_detect != 0: espnet's end detection
+ * (e2e_asr_common.end_detect, M = 3, threshold d_end = log(exp(-10))) stops an utterance early; an empty beam and the last token
+ * always do.  n_steps [U]: tokens searched (rows of hist that are valid for the utterance).
+ * tavsr_ctc_beam_search_ok: 1 when K <= V <= 64 and the LDS of (K, V, T) fits a workgroup, else the entry returns TAVSR_EUNSUPPORTED. */
+int tavsr_ctc_beam_search_ok(int32_t K, int32_t V, int32_t T);
+int tavsr_ctc_beam_search(const float* logp, const int64_t* lens, const int32_t* maxlen, int32_t* hist, int32_t* n_steps, int32_t U,
+                          int32_t K, int32_t T, int32_t V, int32_t hist_steps, int32_t sos, int32_t eos, int32_t blank, float w_ctc,
+                          float add, int32_t end_detect, float d_end, tavsr_stream_t stream);
 /* y = act(x) elementwise (the LM's Linear -> LayerNorm -> ReLU input layer); in place allowed */
 int tavsr_act_fwd(const float* x, float* y, int64_t n, int32_t act, tavsr_stream_t stream);
 

@@ -258,54 +258,50 @@ __device__ __forceinline__ float logaddexp2(float a, float b) {
   const float m = fmaxf(a, b), d = -fabsf(a - b);
   return m + 0.69314718055994530942f * __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(1.4426950408889634f * d));
 }
+// The same with its one multiply-add written as a fused one.  Above, the compiler is free to fuse it or not, and it decides site by
+// site (the unrolled recursion below has both forms, by what the vectoriser paired): two kernels that inline the expression differ
+// in the last bit of some sums.  Kernels that must agree with each other bit for bit use this form.
+__device__ __forceinline__ float logaddexp2_fused(float a, float b) {
+  const float m = fmaxf(a, b), d = -fabsf(a - b);
+  return __builtin_fmaf(0.69314718055994530942f, __builtin_amdgcn_logf(1.f + __builtin_amdgcn_exp2f(1.4426950408889634f * d)), m);
+}
+template <bool PIN>
+__device__ __forceinline__ float logaddexp2_t(float a, float b) { return PIN ? logaddexp2_fused(a, b) : logaddexp2(a, b); }
 
-// One (hypothesis n, candidate column c) of CTCPrefixScoreTH.__call__.  logp [U][T][V] (log-softmax of the CTC head),
-// lens [U].  r_prev [N][T][2] (nb, b) and s_prev [N] of the hypothesis (first == 1: the <sos> state is built here instead).
-// Writes r_new [N][T][2][C], psi [N][C] = log_psi(candidate) - s_prev  and  psi_abs [N][C] = log_psi(candidate);
-// column c == 0 also writes eos [N] = r_sum[len-1] - s_prev and eos_abs.
-__device__ __forceinline__ void ctc_prefix_one(const float* __restrict__ logp, const int64_t* __restrict__ lens,
-                                               const float* __restrict__ r_prev, const float* __restrict__ s_prev,
-                                               const int64_t* __restrict__ last_tok, int tok, float* __restrict__ r_new,
-                                               float* __restrict__ psi, float* __restrict__ psi_abs, float* __restrict__ eos,
-                                               float* __restrict__ eos_abs, int n, int c, int K, int T, int V, int C, int out_len,
-                                               int blank, int first) {
+// The recursion of CTCPrefixScoreTH.__call__ for ONE (hypothesis, token): forward variables r[t] = (nb, b) of the prefix extended
+// by `tok` over the frames of one utterance (lp = its [T][V] log-posteriors, L valid frames), from the hypothesis' own forward
+// variables.  `prev_at(t, pn, pb)` loads them (not called when first == 1: the <sos> state - nb = logzero, b = cumulative blank - is
+// built here), `store(t, nn, nb)` receives every frame of the new ones, t in [0, T).  Returns log_psi of the token.  Shared by
+// ctc_prefix_one (state in global memory) and ctc_beam_search_kernel (state in LDS).  PIN: the arithmetic that does not depend on the
+// compiler's choice of fused multiply-adds (logaddexp2_fused; everything else here is additions) - the one-launch search and the
+// token-by-token CTC-only route it must equal bit for bit; the hybrid search keeps the form it always had.
+template <bool PIN, class Prev, class Store>
+__device__ __forceinline__ float ctc_prefix_recursion(const float* __restrict__ lp, int L, int T, int V, int tok, int blank, int out_len,
+                                                      int first, bool same, Prev prev_at, Store store) {
   const float logzero = -10000000000.0f;
-  const int u = n / K;
-  const int L = (int)lens[u];
-  const float* lp = logp + (int64_t)u * T * V;
-  const float* rp = r_prev + (int64_t)n * T * 2;
-  const float sp = first ? 0.f : s_prev[n];
-  const bool same = !first && tok == (int)last_tok[n];
-  float* rn = r_new + (int64_t)n * T * 2 * C + c;
   // previous forward variables: (nb, b) per frame; <sos>: nb = logzero, b = cumulative blank
   float cum = 0.f;
-  auto prev = [&](int t, float& pn, float& pb) {
-    if (first) { pn = logzero; pb = cum; }     // cum must already hold sum_{t' <= t} logp[t'][blank]
-    else { pn = rp[t * 2]; pb = rp[t * 2 + 1]; }
-  };
   const int start = max(out_len, 1);
-  for (int t = 0; t < start && t < T; ++t) { rn[(int64_t)(t * 2) * C] = logzero; rn[(int64_t)(t * 2 + 1) * C] = logzero; }
+  for (int t = 0; t < start && t < T; ++t) store(t, logzero, logzero);
   float rn_n = logzero, rn_b = logzero;        // r[start - 1]
   if (out_len == 0) {
     rn_n = lp[tok];                            // r[0, nb] = x[0][tok]
-    rn[0] = rn_n;
+    store(0, rn_n, logzero);
   }
   if (first) { for (int t = 0; t < start - 1; ++t) cum += lp[(int64_t)t * V + blank]; }
   // log_psi accumulates logsumexp over t in [start, L) of (phi[t-1] + x[t][tok]) and r[start-1, nb]
   float acc = rn_n;
   if (first) {
     for (int t = start; t < L; ++t) {
-      float pn, pb;
-      cum += lp[(int64_t)(t - 1) * V + blank];
-      prev(t - 1, pn, pb);
-      const float phi = same ? pb : logaddexp2(pn, pb);
+      cum += lp[(int64_t)(t - 1) * V + blank];     // cum = sum_{t' <= t - 1} logp[t'][blank]
+      const float pn = logzero, pb = cum;
+      const float phi = same ? pb : logaddexp2_t<PIN>(pn, pb);
       const float xt = lp[(int64_t)t * V + tok], xb = lp[(int64_t)t * V + blank];
-      const float nn = logaddexp2(rn_n, phi) + xt;
-      const float nb = logaddexp2(rn_n, rn_b) + xb;
-      acc = logaddexp2(acc, phi + xt);
+      const float nn = logaddexp2_t<PIN>(rn_n, phi) + xt;
+      const float nb = logaddexp2_t<PIN>(rn_n, rn_b) + xb;
+      acc = logaddexp2_t<PIN>(acc, phi + xt);
       rn_n = nn; rn_b = nb;
-      rn[(int64_t)(t * 2) * C] = nn;
-      rn[(int64_t)(t * 2 + 1) * C] = nb;
+      store(t, nn, nb);
     }
   } else {
     // The recursion is sequential in t, its INPUTS are not: the four values a frame needs (two posteriors, the previous
@@ -319,39 +315,72 @@ __device__ __forceinline__ void ctc_prefix_one(const float* __restrict__ logp, c
         const int t = min(t0 + j, L - 1);
         xt[j] = lp[(int64_t)t * V + tok];
         xb[j] = lp[(int64_t)t * V + blank];
-        pn[j] = rp[(t - 1) * 2];
-        pb[j] = rp[(t - 1) * 2 + 1];
+        prev_at(t - 1, pn[j], pb[j]);
       }
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const int t = t0 + j;
         if (t < L) {
-          const float phi = same ? pb[j] : logaddexp2(pn[j], pb[j]);
-          const float nn = logaddexp2(rn_n, phi) + xt[j];
-          const float nb = logaddexp2(rn_n, rn_b) + xb[j];
-          acc = logaddexp2(acc, phi + xt[j]);
+          const float phi = same ? pb[j] : logaddexp2_t<PIN>(pn[j], pb[j]);
+          const float nn = logaddexp2_t<PIN>(rn_n, phi) + xt[j];
+          const float nb = logaddexp2_t<PIN>(rn_n, rn_b) + xb[j];
+          acc = logaddexp2_t<PIN>(acc, phi + xt[j]);
           rn_n = nn; rn_b = nb;
-          rn[(int64_t)(t * 2) * C] = nn;
-          rn[(int64_t)(t * 2 + 1) * C] = nb;
+          store(t, nn, nb);
         }
       }
     }
   }
-  for (int t = max(L, start); t < T; ++t) { rn[(int64_t)(t * 2) * C] = logzero; rn[(int64_t)(t * 2 + 1) * C] = logzero; }
-  const float out_psi = tok == blank ? logzero : acc;
+  for (int t = max(L, start); t < T; ++t) store(t, logzero, logzero);
+  return tok == blank ? logzero : acc;
+}
+
+// log_psi of <eos> behind a hypothesis: r_sum of its last valid frame (the <sos> state when first == 1)
+template <bool PIN, class Prev>
+__device__ __forceinline__ float ctc_prefix_eos(const float* __restrict__ lp, int L, int V, int blank, int first, Prev prev_at) {
+  float pn, pb;
+  if (first) {
+    float cum = 0.f;
+    for (int t = 0; t < L; ++t) cum += lp[(int64_t)t * V + blank];
+    pn = -10000000000.0f; pb = cum;
+  } else {
+    prev_at(L - 1, pn, pb);
+  }
+  return logaddexp2_t<PIN>(pn, pb);
+}
+
+// One (hypothesis n, candidate column c) of CTCPrefixScoreTH.__call__.  logp [U][T][V] (log-softmax of the CTC head),
+// lens [U].  r_prev [N][T][2] (nb, b) and s_prev [N] of the hypothesis (first == 1: the <sos> state is built here instead).
+// Writes r_new [N][T][2][C], psi [N][C] = log_psi(candidate) - s_prev  and  psi_abs [N][C] = log_psi(candidate);
+// column c == 0 also writes eos [N] = r_sum[len-1] - s_prev and eos_abs.
+template <bool PIN>
+__device__ __forceinline__ void ctc_prefix_one(const float* __restrict__ logp, const int64_t* __restrict__ lens,
+                                               const float* __restrict__ r_prev, const float* __restrict__ s_prev,
+                                               const int64_t* __restrict__ last_tok, int tok, float* __restrict__ r_new,
+                                               float* __restrict__ psi, float* __restrict__ psi_abs, float* __restrict__ eos,
+                                               float* __restrict__ eos_abs, int n, int c, int K, int T, int V, int C, int out_len,
+                                               int blank, int first) {
+  const int u = n / K;
+  const int L = (int)lens[u];
+  const float* lp = logp + (int64_t)u * T * V;
+  const float* rp = r_prev + (int64_t)n * T * 2;
+  const float sp = first ? 0.f : s_prev[n];
+  const bool same = !first && tok == (int)last_tok[n];
+  float* rn = r_new + (int64_t)n * T * 2 * C + c;
+  auto prev_at = [&](int t, float& pn, float& pb) { pn = rp[t * 2]; pb = rp[t * 2 + 1]; };
+  auto store = [&](int t, float nn, float nb) { rn[(int64_t)(t * 2) * C] = nn; rn[(int64_t)(t * 2 + 1) * C] = nb; };
+  const float out_psi = ctc_prefix_recursion<PIN>(lp, L, T, V, tok, blank, out_len, first, same, prev_at, store);
   psi_abs[(int64_t)n * C + c] = out_psi;
   psi[(int64_t)n * C + c] = out_psi - sp;
   if (c == 0) {
-    float pn, pb;
-    if (first) { cum = 0.f; for (int t = 0; t < L; ++t) cum += lp[(int64_t)t * V + blank]; }
-    prev(L - 1, pn, pb);
-    const float e = logaddexp2(pn, pb);
+    const float e = ctc_prefix_eos<PIN>(lp, L, V, blank, first, prev_at);
     eos_abs[n] = e;
     eos[n] = e - sp;
   }
 }
 
-// thread = (hypothesis n, candidate c), candidates given
+// thread = (hypothesis n, candidate c), candidates given (ALL: cand == NULL, candidate c is token c, C == V)
+template <bool ALL>
 __global__ __launch_bounds__(256) void ctc_prefix_step_kernel(const float* __restrict__ logp, const int64_t* __restrict__ lens,
                                                               const float* __restrict__ r_prev, const float* __restrict__ s_prev,
                                                               const int64_t* __restrict__ last_tok,
@@ -364,8 +393,8 @@ __global__ __launch_bounds__(256) void ctc_prefix_step_kernel(const float* __res
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= N * C) return;
   const int n = i / C, c = i % C;
-  ctc_prefix_one(logp, lens, r_prev, s_prev, last_tok, (int)cand[(int64_t)n * C + c], r_new, psi, psi_abs, eos, eos_abs, n, c, K, T, V,
-                 C, out_len, blank, first);
+  ctc_prefix_one<ALL>(logp, lens, r_prev, s_prev, last_tok, ALL ? c : (int)cand[(int64_t)n * C + c], r_new, psi, psi_abs, eos, eos_abs, n,
+                      c, K, T, V, C, out_len, blank, first);
 }
 
 // wave = hypothesis n.  The pre-beam rides in front of the scorer: the C <= 64 best tokens of full[n][0..V) (espnet's
@@ -416,8 +445,8 @@ __global__ __launch_bounds__(256) void ctc_prefix_topk_kernel(const float* __res
   }
   if (lane < C) {
     cand[(int64_t)n * C + lane] = mytok;
-    ctc_prefix_one(logp, lens, r_prev, s_prev, last_tok, mytok, r_new, psi, psi_abs, eos, eos_abs, n, lane, K, T, V, C, out_len, blank,
-                   first);
+    ctc_prefix_one<false>(logp, lens, r_prev, s_prev, last_tok, mytok, r_new, psi, psi_abs, eos, eos_abs, n, lane, K, T, V, C, out_len,
+                          blank, first);
   }
 }
 
@@ -457,6 +486,11 @@ __global__ __launch_bounds__(256) void beam_combine_kernel(const float* __restri
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int n = blockIdx.x * 4 + wave;
   if (n >= N) return;
+  if (!psi) {      // no CTC scorer: weighted = full + score
+    const float sc = score[n];
+    for (int v = lane; v < V; v += 64) weighted[(int64_t)n * V + v] = full[(int64_t)n * V + v] + sc;
+    return;
+  }
   const float base = -10000000000.0f - s_prev[n], es = eos_s[n], sc = score[n];
   for (int v = lane; v < V; v += 64) {
     float cf = v == eos ? es : base;
@@ -538,6 +572,15 @@ __global__ __launch_bounds__(1024) void beam_combine_topk_kernel(const float* __
   const int u = blockIdx.x;
   for (int k = wave; k < K; k += 16) {      // (16 waves: every beam slot of the usual widths has a wave of its own)
     const int n = u * K + k;
+    if (!psi) {      // no CTC scorer: weighted = full + score
+      const float sc = score[n];
+      for (int v = lane; v < V; v += 64) {
+        const float wv = full[(int64_t)n * V + v] + sc;
+        s_w[k * V + v] = wv;
+        if (weighted) weighted[(int64_t)n * V + v] = wv;
+      }
+      continue;
+    }
     const float base = -10000000000.0f - s_prev[n], es = eos_s[n], sc = score[n];
     for (int v = lane; v < V; v += 64) {
       float cf = v == eos ? es : base;
@@ -583,7 +626,8 @@ __global__ __launch_bounds__(1024) void beam_select_topk_kernel(const float* __r
   if (wave < K) {
     const int n = u * K + wave;
     const bool in = lane < V;
-    float f = in ? dec[(int64_t)n * V + lane] : -INFINITY;
+    // dec == NULL: no decoder term - the row starts from w_lm * log_softmax(z_lm) + add, or from add alone
+    float f = !in ? -INFINITY : dec ? dec[(int64_t)n * V + lane] : z_lm ? 0.f : add;
     if (z_lm) {                    // log_softmax_rows_kernel with alpha = w_lm, accumulate, add - one element per lane
       const float x = in ? z_lm[(int64_t)n * V + lane] : -INFINITY;
       const float mx = wave_max(x);
@@ -600,7 +644,7 @@ __global__ __launch_bounds__(1024) void beam_select_topk_kernel(const float* __r
     if (full_out && in) full_out[(int64_t)n * V + lane] = f;
     // pre-beam: C rounds of the wave's arg-max (ctc_prefix_topk_kernel's selection with the row in one register per lane)
     bool taken = false;
-    for (int c = 0; c < C; ++c) {
+    for (int c = 0; psi_all && c < C; ++c) {      // (psi_all == NULL: no CTC scorer, no pre-beam)
       const float mine = (in && !taken) ? f : -INFINITY;
       const float m = wave_max_dpp(mine);
       int bi = wave_min_dpp((in && !taken && mine == m) ? lane : 0x7fffffff);
@@ -608,7 +652,11 @@ __global__ __launch_bounds__(1024) void beam_select_topk_kernel(const float* __r
       if (bi == lane) taken = true;
       if (cand_out && lane == 0) cand_out[(int64_t)n * C + c] = bi;
     }
-    if (in) {
+    if (in && !psi_all) {      // weighted = full + score
+      const float wv = f + score[n];
+      s_w[wave * V + lane] = wv;
+      if (weighted) weighted[(int64_t)n * V + lane] = wv;
+    } else if (in) {
       const float base = -10000000000.0f - s_prev[n], es = eos_s[n], sc = score[n];
       const float cf = lane == eos ? es : (taken ? psi_all[(int64_t)n * V + lane] : base);
       {
@@ -625,6 +673,164 @@ __global__ __launch_bounds__(1024) void beam_select_topk_kernel(const float* __r
   __syncthreads();
   if (wave != 0) return;
   beam_topk_rounds(s_w, K * V, K, u, top_s, top_i, lane);
+}
+
+// ---- the whole CTC prefix beam search of an utterance in ONE launch -------------------------------------------------------------
+// Scorers {CTC prefix scorer, length bonus}, no pre-beam (espnet BatchBeamSearch with ctc_weight 1: avsr_inference.py:141-153, 277-304,
+// run at :449-518): one token of the search has no neural chain - it is the prefix recursion over the frames, a top-K and the
+// re-ordering of K small state vectors.  One workgroup per utterance walks ALL its tokens; the forward variables r[K][T][2] of the beam
+// live in two LDS buffers (previous / next token) and never leave them.  Wave w owns beam slots w, w + nw, ...; lane v owns token v.
+//   phase A  psi[k][v], <eos> score: ctc_prefix_recursion<PIN> (tavsr_ctc_prefix_step's cand == NULL form, bit for bit) from r_prev[k]
+//            (LDS, every lane of a wave reads the same word) and logp[u][t][v] (global, stays in L2); nothing is stored per frame
+//   phase B  weighted = add + w_ctc * (psi - s_prev) + score (beam_select_topk_kernel's arithmetic, dec = z_lm = NULL, C = V), then
+//            beam_topk_rounds on wave 0
+//   phase C  every winner (slot, token): the recursion once more, this time storing r_next[j] - one winner per wave at a time
+// plus the bookkeeping of a captured step (beam_reorder_kernel with maxlen: records in hist, ended hypotheses leave the beam) and
+// espnet's end detection (the rule of the host's per-token processing) on wave 0.  Loops are bounded by T frames and maxlen[u] tokens;
+// the workgroup waits on nobody but itself.
+// offsets in 4-byte words into the dynamic LDS block.  The double-buffered parts are base + buffer * stride (plain scalars: an array
+// indexed by the buffer would live in scratch): r [2][K][T][2], and st [2][3][K] = (s_prev, score, last token) of the K slots
+struct CtcSearchLds {
+  int r, r_stride, top_i, top_s, s_w, st, st_stride, eos_abs, best_len, flag, words;
+};
+__host__ __device__ inline CtcSearchLds ctc_search_lds(int K, int V, int T) {
+  CtcSearchLds o;
+  int p = 0;
+  o.r = p; o.r_stride = K * T * 2; p += 2 * o.r_stride;
+  o.top_i = p; p += 2 * K;                  // int64 (the offset is even: 8-byte aligned)
+  o.top_s = p; p += K;
+  o.s_w = p; p += K * V;
+  o.st = p; o.st_stride = 3 * K; p += 2 * o.st_stride;
+  o.eos_abs = p; p += K;
+  o.best_len = p; p += T + 4;
+  o.flag = p; p += 2;
+  o.words = p;
+  return o;
+}
+constexpr int kCtcSearchLdsBytes = 160 * 1024;
+
+__global__ __launch_bounds__(1024) void ctc_beam_search_kernel(const float* __restrict__ logp, const int64_t* __restrict__ lens,
+                                                              const int32_t* __restrict__ maxlen, int32_t* __restrict__ hist,
+                                                              int32_t* __restrict__ n_steps, int U, int K, int T, int V,
+                                                              int hist_steps, int sos, int eos, int blank, float w_ctc, float add,
+                                                              int end_detect, float d_end) {
+  extern __shared__ __align__(16) float lds[];
+  const CtcSearchLds o = ctc_search_lds(K, V, T);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
+  const int u = blockIdx.x, N = U * K;
+  const int L = min(max((int)lens[u], 1), T);
+  const int ntok = min(min(maxlen[u], L), hist_steps);      // a prefix is never longer than its input
+  const float* lp = logp + (int64_t)u * T * V;
+  float* s_w = lds + o.s_w;
+  float* top_s = lds + o.top_s;
+  int64_t* top_i = reinterpret_cast<int64_t*>(lds + o.top_i);
+  float* eos_abs = lds + o.eos_abs;
+  float* best_len = lds + o.best_len;
+  int* flag = reinterpret_cast<int*>(lds + o.flag);
+  // <sos>: one live hypothesis in slot 0 (its forward variables are built by the recursion itself, first == 1)
+  for (int k = threadIdx.x; k < K; k += blockDim.x) {
+    lds[o.st + k] = 0.f;                                    // s_prev
+    lds[o.st + K + k] = k == 0 ? 0.f : -INFINITY;           // score
+    reinterpret_cast<int*>(lds)[o.st + 2 * K + k] = sos;    // last token
+  }
+  for (int t = threadIdx.x; t < T + 4; t += blockDim.x) best_len[t] = -INFINITY;
+  if (threadIdx.x == 0) flag[0] = 0;
+  float best = -INFINITY;                                   // best ended score (wave 0)
+  int done = 0;
+  __syncthreads();
+  for (int step = 0; step < ntok; ++step) {
+    const int cur = step & 1, nxt = cur ^ 1;
+    const int first = step == 0;
+    const float* r_cur = lds + o.r + cur * o.r_stride;
+    float* r_nxt = lds + o.r + nxt * o.r_stride;
+    const float* s_cur = lds + o.st + cur * o.st_stride;
+    const float* sc_cur = s_cur + K;
+    const int* tok_cur = reinterpret_cast<const int*>(s_cur) + 2 * K;
+    float* s_nxt = lds + o.st + nxt * o.st_stride;
+    // phase A + B: prefix scores of (slot k, token lane) and the weighted scores
+    for (int k = wave; k < K; k += nw) {
+      const float* rp = r_cur + k * T * 2;
+      auto prev_at = [&](int t, float& pn, float& pb) { pn = rp[t * 2]; pb = rp[t * 2 + 1]; };
+      auto drop = [](int, float, float) {};
+      const float sp = first ? 0.f : s_cur[k];
+      if (lane < V) {
+        const bool same = !first && lane == tok_cur[k];
+        const float out_psi = ctc_prefix_recursion<true>(lp, L, T, V, lane, blank, step, first, same, prev_at, drop);
+        const float psi = out_psi - sp;
+        float es = 0.f;
+        if (lane == eos) {
+          const float e = ctc_prefix_eos<true>(lp, L, V, blank, first, prev_at);
+          eos_abs[k] = e;
+          es = e - sp;
+        }
+        const float cf = lane == eos ? es : psi;
+        {
+#pragma clang fp contract(off)
+          const float prod = w_ctc * cf;
+          const float sum = add + prod;
+          s_w[k * V + lane] = sum + sc_cur[k];
+        }
+      }
+    }
+    __syncthreads();
+    if (wave == 0) beam_topk_rounds(s_w, K * V, K, 0, top_s, top_i, lane);
+    __syncthreads();
+    const bool last = step + 1 >= ntok;
+    // phase C: the winners' forward variables into the other buffer.  The recursion of a winner is ONE dependent chain: every lane of
+    // the wave runs it and stores the same values to the same words - deliberately.  A single active lane would take the same time (a
+    // wave issues an instruction for one lane or for 64 alike), and the uniform form keeps the loads of r_prev / logp broadcasts.
+    for (int j = wave; j < K; j += nw) {
+      const int ti = (int)top_i[j];
+      const int prev = ti / V, tk = ti % V;
+      const float* rp = r_cur + prev * T * 2;
+      float* rn = r_nxt + j * T * 2;
+      auto prev_at = [&](int t, float& pn, float& pb) { pn = rp[t * 2]; pb = rp[t * 2 + 1]; };
+      auto keep = [&](int t, float nn, float nb) { rn[t * 2] = nn; rn[t * 2 + 1] = nb; };
+      const bool same = !first && tk == tok_cur[prev];
+      const float out_psi = ctc_prefix_recursion<true>(lp, L, T, V, tk, blank, step, first, same, prev_at, keep);
+      if (lane == 0) s_nxt[j] = tk == eos ? eos_abs[prev] : out_psi;
+    }
+    // bookkeeping of the token on wave 0, lane j = new hypothesis j
+    if (wave == 0) {
+      const bool in = lane < K;
+      const float ts = in ? top_s[lane] : -INFINITY;
+      const int ti = in ? (int)top_i[lane] : 0;
+      const int prev = ti / V, tk = ti % V;
+      if (in) {
+        s_nxt[K + lane] = (tk == eos || last) ? -INFINITY : ts;
+        reinterpret_cast<int*>(s_nxt)[2 * K + lane] = tk;
+        int32_t* h = hist + (int64_t)step * 3 * N + u * K + lane;      // (token, extended slot, score bits)
+        h[0] = tk;
+        h[N] = prev + u * K;
+        h[2 * N] = __float_as_int(ts);
+      }
+      // end detection: hypotheses that end here, the best ended score, the best ended score of the three most recent lengths
+      const bool valid = in && ts - ts == 0.f;                          // finite
+      const bool take = valid && (tk == eos || last);
+      const float m = wave_max(take ? ts : -INFINITY);
+      const int running = __popcll(__ballot(valid && !take));
+      if (m > -INFINITY) {
+        best = fmaxf(best, m);
+        const int ln = last ? step + 3 : step + 2;
+        if (lane == 0) best_len[ln] = fmaxf(best_len[ln], m);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      int count = 0;
+      for (int q = 0; q < 3; ++q)
+        if (step - q >= 0) {
+          const float bl = best_len[step - q];
+          if (bl - bl == 0.f && bl - best < d_end) ++count;
+        }
+      if (!end_detect) count = 0;
+      if (lane == 0) flag[0] = (count == 3 || running == 0 || last) ? 1 : 0;
+    }
+    __syncthreads();
+    done = step + 1;
+    if (flag[0]) break;      // (rewritten only behind the next token's two barriers: every wave has read it by then)
+  }
+  if (threadIdx.x == 0) n_steps[u] = done;
 }
 
 // After the top-k over (beam slot, token) of every utterance (top_i [U][K] = slot * V + token): hypothesis n extends slot
@@ -646,17 +852,17 @@ __global__ __launch_bounds__(256) void beam_reorder_kernel(const int64_t* __rest
   const int64_t ti = top_i[n];
   const int prev = (int)(ti / V) + u * K, tk = (int)(ti % V);
   int cidx = 0;                                                   // first candidate column equal to the token (argmax of ==)
-  for (int c = C - 1; c >= 0; --c)
+  for (int c = C - 1; r_new && c >= 0; --c)                       // (r_new == NULL: no CTC state to gather)
     if ((int)cand[(int64_t)prev * C + c] == tk) cidx = c;
   const int step = *step_dev;
-  for (int e = threadIdx.x; e < T * 2; e += 256) r_out[(int64_t)n * T * 2 + e] = r_new[((int64_t)prev * T * 2 + e) * C + cidx];
+  for (int e = threadIdx.x; r_new && e < T * 2; e += 256) r_out[(int64_t)n * T * 2 + e] = r_new[((int64_t)prev * T * 2 + e) * C + cidx];
   for (int e = threadIdx.x; e < ld_y; e += 256) yseq_out[(int64_t)n * ld_y + e] = e == step + 1 ? (int64_t)tk : yseq[(int64_t)prev * ld_y + e];
   // maxlen given: the head of the NEXT step rides along (tavsr_beam_step_begin for step + 1: a hypothesis that just took <eos>, or whose
   // utterance has used up its token budget, leaves the beam; column step + 1 of the ancestor list names the next step's own row)
   for (int e = threadIdx.x; e < ld_a; e += 256)
     anc_out[(int64_t)n * ld_a + e] = (maxlen && e == step + 1) ? n + (step + 1) * N : anc[(int64_t)prev * ld_a + e];
   if (threadIdx.x == 0) {
-    s_out[n] = psi_abs[(int64_t)prev * C + cidx];
+    if (r_new) s_out[n] = psi_abs[(int64_t)prev * C + cidx];
     tok_out[n] = tk;
     score_out[n] = (maxlen && (tk == eos || step + 1 >= maxlen[u])) ? -INFINITY : top_s[n];
     if (hist && step < hist_steps) {          // back-pointer record of this token: (token, extended slot, score bits)
@@ -1046,12 +1252,18 @@ extern "C" int tavsr_ctc_prefix_step(const float* logp, const int64_t* lens, con
                                      const int64_t* last_tok, const int64_t* cand, float* r_new, float* psi, float* psi_abs,
                                      float* eos, float* eos_abs, int32_t N, int32_t K, int32_t T, int32_t V, int32_t C,
                                      int32_t out_len, int32_t blank, const int32_t* step_dev, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(logp && lens && cand && r_new && psi && psi_abs && eos && eos_abs, TAVSR_EINVAL, "ctc_prefix_step: null pointer");
+  TAVSR_REQUIRE(logp && lens && r_new && psi && psi_abs && eos && eos_abs, TAVSR_EINVAL, "ctc_prefix_step: null pointer");
+  TAVSR_REQUIRE(cand || C == V, TAVSR_EINVAL, "ctc_prefix_step: without a candidate list every token is scored, C must be V (got %d, %d)", C, V);
   TAVSR_REQUIRE((out_len == 0 && !step_dev) || (r_prev && s_prev && last_tok), TAVSR_EINVAL, "ctc_prefix_step: state needed after <sos>");
   TAVSR_REQUIRE(N > 0 && K > 0 && N % K == 0 && C > 0, TAVSR_EINVAL, "ctc_prefix_step: bad sizes");
-  hipLaunchKernelGGL(ctc_prefix_step_kernel, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logp,
-                     lens, r_prev, s_prev, last_tok, cand, r_new, psi, psi_abs, eos, eos_abs, N, K, T, V, C, out_len, blank,
-                     out_len == 0 ? 1 : 0, step_dev);
+  if (cand)
+    hipLaunchKernelGGL(ctc_prefix_step_kernel<false>, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logp,
+                       lens, r_prev, s_prev, last_tok, cand, r_new, psi, psi_abs, eos, eos_abs, N, K, T, V, C, out_len, blank,
+                       out_len == 0 ? 1 : 0, step_dev);
+  else
+    hipLaunchKernelGGL(ctc_prefix_step_kernel<true>, dim3((unsigned)((N * C + 255) / 256)), dim3(256), 0, (hipStream_t)stream, logp,
+                       lens, r_prev, s_prev, last_tok, cand, r_new, psi, psi_abs, eos, eos_abs, N, K, T, V, C, out_len, blank,
+                       out_len == 0 ? 1 : 0, step_dev);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
 }
@@ -1089,7 +1301,7 @@ extern "C" int tavsr_log_softmax_rows(const float* x, int64_t ldx, float* y, int
 extern "C" int tavsr_beam_combine(const float* full, const int64_t* cand, const float* psi, float* psi_abs, const float* eos_s,
                                   const float* eos_abs, const float* s_prev, const float* score, float* weighted, int32_t N,
                                   int32_t V, int32_t C, int32_t eos, float w_ctc, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(full && cand && psi && psi_abs && eos_s && eos_abs && s_prev && score && weighted, TAVSR_EINVAL,
+  TAVSR_REQUIRE(full && score && weighted && (!psi || (cand && psi_abs && eos_s && eos_abs && s_prev)), TAVSR_EINVAL,
                 "beam_combine: null pointer");
   if (N <= 0) return TAVSR_OK;
   hipLaunchKernelGGL(beam_combine_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, full, cand, psi, psi_abs,
@@ -1102,7 +1314,7 @@ extern "C" int tavsr_beam_combine_topk(const float* full, const int64_t* cand, c
                                        const float* eos_abs, const float* s_prev, const float* score, float* weighted, float* top_s,
                                        int64_t* top_i, int32_t N, int32_t K, int32_t V, int32_t C, int32_t eos, float w_ctc,
                                        tavsr_stream_t stream) {
-  TAVSR_REQUIRE(full && cand && psi && psi_abs && eos_s && eos_abs && s_prev && score && top_s && top_i, TAVSR_EINVAL,
+  TAVSR_REQUIRE(full && score && top_s && top_i && (!psi || (cand && psi_abs && eos_s && eos_abs && s_prev)), TAVSR_EINVAL,
                 "beam_combine_topk: null pointer");
   TAVSR_REQUIRE(N > 0 && K > 0 && N % K == 0 && V > 0 && K <= V, TAVSR_EINVAL, "beam_combine_topk: bad sizes");
   TAVSR_REQUIRE((int64_t)K * V <= kTopkMax, TAVSR_EUNSUPPORTED,
@@ -1118,8 +1330,9 @@ extern "C" int tavsr_beam_select_topk(const float* dec, const float* z_lm, float
                                       const float* eos_s, const float* eos_abs, const float* s_prev, const float* score, float* full_out,
                                       float* weighted, int64_t* cand_out, float* top_s, int64_t* top_i, int32_t N, int32_t K, int32_t V,
                                       int32_t C, int32_t eos, float w_ctc, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(dec && psi_all && psi_abs_all && eos_s && eos_abs && s_prev && score && top_s && top_i, TAVSR_EINVAL,
+  TAVSR_REQUIRE(score && top_s && top_i && (!psi_all || (psi_abs_all && eos_s && eos_abs && s_prev)), TAVSR_EINVAL,
                 "beam_select_topk: null pointer");
+  TAVSR_REQUIRE(dec || psi_all, TAVSR_EINVAL, "beam_select_topk: neither decoder nor CTC scores - nothing to search on");
   TAVSR_REQUIRE(N > 0 && K > 0 && N % K == 0 && V > 0 && K <= V && C > 0 && C <= V && eos >= 0 && eos < V, TAVSR_EINVAL,
                 "beam_select_topk: bad sizes");
   TAVSR_REQUIRE(V <= 64 && K <= 16, TAVSR_EUNSUPPORTED,
@@ -1145,9 +1358,9 @@ extern "C" int tavsr_beam_reorder_begin(const int64_t* top_i, const float* top_s
                                         int64_t* yseq_out, int32_t* anc_out, int64_t* tok_out, float* score_out, int32_t N, int32_t K,
                                         int32_t V, int32_t C, int32_t T, int32_t ld_y, int32_t ld_a, const int32_t* step_dev,
                                         int32_t* hist, int32_t hist_steps, const int32_t* maxlen, int32_t eos, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(top_i && top_s && cand && r_new && psi_abs && yseq && anc && r_out && s_out && yseq_out && anc_out && tok_out &&
-                    score_out && step_dev, TAVSR_EINVAL, "beam_reorder: null pointer");
-  TAVSR_REQUIRE(r_out != r_new && (const int64_t*)yseq_out != yseq && (const int32_t*)anc_out != anc, TAVSR_EINVAL,
+  TAVSR_REQUIRE(top_i && top_s && yseq && anc && yseq_out && anc_out && tok_out && score_out && step_dev &&
+                    (!r_new || (cand && psi_abs && r_out && s_out)), TAVSR_EINVAL, "beam_reorder: null pointer");
+  TAVSR_REQUIRE((!r_new || r_out != r_new) && (const int64_t*)yseq_out != yseq && (const int32_t*)anc_out != anc, TAVSR_EINVAL,
                 "beam_reorder: the state is re-ordered, outputs must not alias the inputs");
   TAVSR_REQUIRE(N > 0 && K > 0 && N % K == 0, TAVSR_EINVAL, "beam_reorder: bad sizes");
   hipLaunchKernelGGL(beam_reorder_kernel, dim3((unsigned)N), dim3(256), 0, (hipStream_t)stream, top_i, top_s, cand, r_new, psi_abs, yseq,
@@ -1163,6 +1376,35 @@ extern "C" int tavsr_beam_step_begin(float* score, const int64_t* tok, int32_t* 
   TAVSR_REQUIRE(N > 0 && K > 0 && N % K == 0, TAVSR_EINVAL, "beam_step_begin: bad sizes");
   hipLaunchKernelGGL(beam_step_begin_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, (hipStream_t)stream, score, tok, anc, ld_a,
                      maxlen, N, K, eos, step_dev);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
+// LDS the one-launch search needs against what a workgroup may take: the host asks before it routes a search here
+extern "C" int tavsr_ctc_beam_search_ok(int32_t K, int32_t V, int32_t T) {
+  if (K < 1 || V < 1 || T < 1 || V > 64 || K > V || T > (1 << 20)) return 0;
+  if ((int64_t)K * T * 4 > kCtcSearchLdsBytes / 4) return 0;      // (before the exact count: no overflow in it)
+  return (int64_t)ctc_search_lds(K, V, T).words * 4 <= kCtcSearchLdsBytes;
+}
+
+extern "C" int tavsr_ctc_beam_search(const float* logp, const int64_t* lens, const int32_t* maxlen, int32_t* hist, int32_t* n_steps,
+                                     int32_t U, int32_t K, int32_t T, int32_t V, int32_t hist_steps, int32_t sos, int32_t eos,
+                                     int32_t blank, float w_ctc, float add, int32_t end_detect, float d_end, tavsr_stream_t stream) {
+  TAVSR_REQUIRE(logp && lens && maxlen && hist && n_steps, TAVSR_EINVAL, "ctc_beam_search: null pointer");
+  TAVSR_REQUIRE(U > 0 && K > 0 && T > 0 && V > 0 && hist_steps > 0 && sos >= 0 && sos < V && eos >= 0 && eos < V && blank >= 0 && blank < V,
+                TAVSR_EINVAL, "ctc_beam_search: bad sizes");
+  TAVSR_REQUIRE(tavsr_ctc_beam_search_ok(K, V, T), TAVSR_EUNSUPPORTED,
+                "ctc_beam_search: beam %d x %d frames x %d tokens does not fit one workgroup's LDS (tavsr_ctc_beam_search_ok): run the "
+                "search token by token (tavsr_ctc_prefix_step + tavsr_beam_combine_topk + tavsr_beam_reorder)", K, T, V);
+  const size_t bytes = (size_t)ctc_search_lds(K, V, T).words * 4;
+  if (bytes > 48 * 1024) {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ctc_beam_search_kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, kCtcSearchLdsBytes);
+    TAVSR_REQUIRE(e == hipSuccess, TAVSR_EUNSUPPORTED, "ctc_beam_search: hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
+  const int nw = K < 16 ? K : 16;
+  hipLaunchKernelGGL(ctc_beam_search_kernel, dim3((unsigned)U), dim3((unsigned)(64 * nw)), bytes, (hipStream_t)stream, logp, lens, maxlen,
+                     hist, n_steps, U, K, T, V, hist_steps, sos, eos, blank, w_ctc, add, end_detect, d_end);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
 }

@@ -14,6 +14,10 @@ advance together (the reference decodes one utterance at a time on the CPU):
 * The per-step bookkeeping (top-k, ancestor-list gathers, ended-hypothesis lists, end detection) is torch / host code:
   index plumbing on [N]-sized tensors.
 
+* The scorer set is espnet's: a scorer that is None or has weight 0 drops out (a model without decoder: CTC prefix beam search, with
+  or without LM; a model without CTC head: attention beam search).  Scorers {ctc, length_bonus} without pre-beam are searched in ONE
+  launch per batch (``tavsr_ctc_beam_search``: the beam's lattice stays in LDS), the host replaying its bookkeeping over the records.
+
 ``decode(enc, enc_lens)`` takes encoder outputs (``model.encode``), returns per utterance the ended hypotheses sorted
 by score as (token ids incl. <sos>/<eos>, score).  ``Speech2Text`` wraps model + search like the reference's class.
 """
@@ -83,6 +87,10 @@ PREBEAM_FUSED = True   # pre-beam top-k inside the CTC prefix launch
 RECORD_QUEUE = os.environ.get("TAVSR_RECORD_QUEUE", "0") == "1"
 LN_IN_EPILOGUE = True      # batched steps: tavsr_gemm_ln at the x + f(x) -> norm(x) seams
 CTC_BESIDE_SCORERS = True
+# A CTC-only search without LM (scorers {ctc, length_bonus}, no pre-beam) has no neural chain per token: the whole search of an
+# utterance is ONE launch, the beam's forward variables resident in LDS (tavsr_ctc_beam_search), where its shape fits
+# (ops.ctc_beam_search_ok); False: token by token like every other scorer set
+CTC_SEARCH_FUSED = True
 
 
 class _Normed:
@@ -306,13 +314,22 @@ class _LMStep:
 
 class BatchBeamSearch:
     def __init__(self, model, lm=None, beam_size: int = 10, ctc_weight: float = 0.1, lm_weight: float = 0.6,
-                 penalty: float = 0.5, maxlenratio: float = 0.0, minlenratio: float = 0.0):
-        if model.decoder is None or model.ctc is None:
-            raise ValueError("the hybrid search needs both the attention decoder and the CTC head (0 < ctc_weight < 1)")
+                 penalty: float = 0.5, maxlenratio: float = 0.0, minlenratio: float = 0.0, skip_zero_weight: bool = False):
         if not (0.0 <= ctc_weight <= 1.0):
             raise ValueError(f"ctc_weight must lie in [0, 1]: {ctc_weight}")
-        # ctc_weight 0 / 1: espnet skips a scorer whose weight is 0; here its launches still run and enter the sums with
-        # weight 0 (finite log-probabilities), which selects the same hypotheses
+        # The scorer set is espnet's (BeamSearch.__init__ drops a scorer that is None or has weight 0; avsr_inference.py:141-153):
+        # a model without decoder (ctc_weight 1.0 in its model_conf) or without CTC head (0.0) is searched with what it has.  A model
+        # that has BOTH modules keeps every launch it had whatever ctc_weight says - a scorer of weight 0 still runs and enters the sums
+        # with weight 0 (finite log-probabilities), which selects the same hypotheses - unless ``skip_zero_weight`` asks for espnet's set.
+        hybrid = model.decoder is not None and model.ctc is not None
+        drop = skip_zero_weight or not hybrid
+        self.has_dec = model.decoder is not None and not (drop and 1.0 - ctc_weight == 0.0)
+        self.has_ctc = model.ctc is not None and not (drop and ctc_weight == 0.0)
+        self.has_lm = lm is not None and lm_weight != 0.0
+        if not self.has_dec and not self.has_ctc:
+            raise ValueError(f"no scorer is left to search with: the model has {'no' if model.decoder is None else 'a'} decoder and "
+                             f"{'no' if model.ctc is None else 'a'} CTC head, and ctc_weight = {ctc_weight} gives the one it has weight 0. "
+                             f"Set ctc_weight to {1.0 if model.decoder is None else 0.0}")
         # espnet BeamSearch.forward: maxlenratio == 0 -> up to T tokens with end detection; > 0 -> max(1, int(ratio * T)) tokens,
         # < 0 -> -int(ratio) tokens, both without end detection; minlenratio is accepted and (as in espnet 202402) only logged
         self.maxlenratio, self.minlenratio = float(maxlenratio), float(minlenratio)
@@ -325,11 +342,23 @@ class BatchBeamSearch:
         self.w_len = penalty
         # avsr_inference.py:298: pre_beam_score_key = None when ctc_weight == 1 -> the CTC prefix scorer sees every token
         self.C = self.V if ctc_weight == 1.0 else min(int(1.5 * beam_size), self.V)
+        # espnet's do_pre_beam: a partial scorer is present, ctc_weight != 1 (pre_beam_score_key = None there) and fewer candidates than tokens
+        self.pre_beam = self.has_ctc and ctc_weight != 1.0 and int(1.5 * beam_size) < self.V
+        if self.pre_beam and not self.has_dec and not self.has_lm:
+            raise ValueError(f"ctc_weight = {ctc_weight} on a model without decoder and without LM: the pre-beam of the CTC prefix scorer "
+                             "would rank the length bonus alone, a constant - which candidates it keeps is not defined.  Set "
+                             "ctc_weight: 1.0 (CTC prefix beam search over every token), or add an LM")
         self._pinned = None
         self._copy_q = None        # the queue the per-token records leave on (created with the first captured search)
         self._captured = None      # the captured step of the last batch shape (buffers + hipGraph), re-used while the shape repeats
-        self.dec_step = _DecoderStep(model.decoder)
-        self.lm_step = _LMStep(lm) if (lm is not None and lm_weight != 0.0) else None
+        self.n_steps = None        # tokens searched per utterance in the last decode()
+        self.dec_step = _DecoderStep(model.decoder) if self.has_dec else None
+        self.lm_step = _LMStep(lm) if self.has_lm else None
+
+    @property
+    def scorers(self):
+        """names of the scorers the search runs (espnet's keys)"""
+        return tuple(k for k, on in (("decoder", self.has_dec), ("ctc", self.has_ctc), ("length_bonus", True), ("lm", self.has_lm)) if on)
 
     @torch.no_grad()
     def decode(self, enc: torch.Tensor, enc_lens: torch.Tensor, nbest: Optional[int] = None):
@@ -347,7 +376,8 @@ class BatchBeamSearch:
             maxl_h = [-1 * int(self.maxlenratio)] * U
         else:
             maxl_h = [max(1, int(self.maxlenratio * t)) for t in lens_h]
-        if any(m > t for m, t in zip(maxl_h, lens_h)):
+        has_dec, has_ctc = self.has_dec, self.has_ctc
+        if has_ctc and any(m > t for m, t in zip(maxl_h, lens_h)):
             # espnet's CTCPrefixScoreTH indexes its forward variables by output length: a hypothesis longer than the number
             # of frames raises IndexError there; refused up front here
             raise ValueError(f"maxlenratio {self.maxlenratio} asks for more tokens than encoder frames {lens_h}: "
@@ -355,26 +385,123 @@ class BatchBeamSearch:
         steps = max(maxl_h)
         ctc = self.model.ctc
         # derived weight copies follow the parameters (an optimizer step / load_state_dict since the last call): ADVICE round 4
-        self.dec_step.weights.sync()
+        if has_dec:
+            self.dec_step.weights.sync()
         if self.lm_step is not None:
             self.lm_step.sync_weights()
+        # scorers {ctc, length_bonus} without pre-beam: the whole search is one launch where the beam's lattice fits a workgroup's LDS
+        fused = has_ctc and not has_dec and self.lm_step is None and not self.pre_beam and CTC_SEARCH_FUSED and ops.ctc_beam_search_ok(K, V, T)
+        # host-side bookkeeping, vectorised over utterances ([U] / [N]-sized CPU tensors)
+        lens_c = torch.tensor(maxl_h)                               # per-utterance maxlen: the last iteration closes every hypothesis
+        active = torch.ones(U, dtype=torch.bool)
+        n_host = torch.zeros(U, dtype=torch.int32)                  # tokens searched per utterance
+        best = torch.full((U,), -float("inf"))                      # best ended score per utterance
+        best_len = torch.full((U, steps + 4), -float("inf"))        # best ended score per (utterance, hypothesis length)
+        D_end = math.log(1 * math.exp(-10))
+        NEG_INF = -float("inf")
+        ended = [[] for _ in range(U)]
+
+        def host_step(i, tok_h, score_h, rows_of):
+            """espnet post_process / end_detect for token i of every utterance: collects the hypotheses that end here
+            (``rows_of(slot indices)`` -> their token lists incl. <sos>), returns the slots to retire."""
+            nonlocal active
+            n_host.add_(active.to(torch.int32))
+            valid = torch.isfinite(score_h).view(U, K) & active.view(U, 1)
+            last = (lens_c - 1 == i).view(U, 1)
+            # espnet appends <eos> to EVERY hypothesis of the last iteration (also to the ones that just ended)
+            take = valid & ((tok_h.view(U, K) == self.eos) | last)
+            if bool(take.any()):
+                idx = take.view(N).nonzero().view(-1)
+                us = idx // K
+                lns = torch.where(last.view(U)[us], torch.full_like(us, i + 3), torch.full_like(us, i + 2))
+                scs = score_h[idx]
+                for ys, u_, ln, sc in zip(rows_of(idx), us.tolist(), lns.tolist(), scs.tolist()):
+                    ys = (ys + [self.eos] * 2)[:ln]
+                    ys[ln - 1] = self.eos
+                    ended[u_].append((ys, sc))
+                best.index_reduce_(0, us, scs, "amax")
+                flat = us * best_len.shape[1] + lns
+                best_len.view(-1).index_reduce_(0, flat, scs, "amax")
+            running = (valid & ~take).sum(dim=1)
+            count = torch.zeros(U, dtype=torch.int64)
+            for m in range(3):                                     # end_detect: M = 3 most recent lengths
+                if i - m >= 0:
+                    bl = best_len[:, i - m]
+                    count += (torch.isfinite(bl) & (bl - best < D_end)).to(torch.int64)
+            if self.maxlenratio != 0.0:                            # end_detect runs only for maxlenratio == 0
+                count.zero_()
+            stop = (count == 3) | (running == 0) | last.view(U)
+            active = active & ~stop
+            return (take | ~active.view(U, 1)).view(N)
+
+        def rows_from_records(i):
+            def rows_of(idx):
+                out_rows = []
+                for n in idx.tolist():
+                    toks, cur = [], n
+                    for t in range(i, -1, -1):                  # back-track: token of slot `cur`, then the slot it extended
+                        toks.append(int(rec[t, 0, cur]))
+                        cur = int(rec[t, 1, cur])
+                    out_rows.append([self.sos] + toks[::-1])
+                return out_rows
+            return rows_of
+
+        def nbest_lists():
+            self.n_steps = n_host.tolist()
+            out = []
+            for u in range(U):
+                hyps = sorted(ended[u], key=lambda h: h[1], reverse=True)
+                out.append(hyps if nbest is None else hyps[:nbest])
+            return out
+
+        if fused:
+            # One launch searches every utterance to its end (tavsr_ctc_beam_search: records, retiring and end detection on the device);
+            # the host then replays its own per-token processing over the records of the tokens the device searched.
+            key = ("ctc_search", U, T, D, steps, str(dev))
+            cap = self._captured if (self._captured is not None and self._captured["key"] == key) else None
+            if cap is None:
+                cap = self._captured = dict(key=key, graph=None, logp_ctc=ops.empty(U, T, V, like=enc),
+                                            enc_lens=torch.empty(U, dtype=torch.int64, device=dev),
+                                            maxl=torch.empty(U, dtype=torch.int32, device=dev),
+                                            hist=torch.zeros(steps, 3, N, dtype=torch.int32, device=dev),
+                                            n_steps=torch.zeros(U, dtype=torch.int32, device=dev))
+            cap["enc_lens"].copy_(enc_lens)
+            cap["maxl"].copy_(torch.tensor(maxl_h, dtype=torch.int32))
+            ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias), out=cap["logp_ctc"].view(U * T, V))
+            ops.ctc_beam_search(cap["logp_ctc"], cap["enc_lens"], cap["maxl"], cap["hist"], cap["n_steps"], K, self.sos, self.eos,
+                                self.w_ctc, self.w_len, self.maxlenratio == 0.0, D_end)
+            n_dev = cap["n_steps"].cpu()
+            searched = int(n_dev.max())
+            rec = cap["hist"][:searched].cpu().numpy()
+            for i in range(searched):
+                host_step(i, torch.from_numpy(rec[i, 0]).to(torch.int64), torch.from_numpy(rec[i, 2]).view(torch.float32), rows_from_records(i))
+            if bool(active.any()) or not torch.equal(n_host, n_dev):
+                raise RuntimeError(f"tavsr_ctc_beam_search stopped after {n_dev.tolist()} tokens per utterance, the host's end detection "
+                                   f"over its records after {n_host.tolist()} (still searching: {active.tolist()})")
+            return nbest_lists()
         # A captured step is tied to its buffers, not to a batch: while the shape (utterances, frames, token budget) repeats -
         # a stream of 4 s clips - the buffers are refilled in place and the hipGraph of the previous call is replayed; capture
         # and warm-up were 8-10 ms of a 95 ms batch-1 search.
-        key = (U, T, D, steps, str(dev), self.lm_step is not None)
+        key = (U, T, D, steps, str(dev), self.scorers)
         cap = self._captured if (GRAPH_STEP and self._captured is not None and self._captured["key"] == key) else None
         if cap is not None:
             logp_ctc, lens_buf = cap["logp_ctc"], cap["enc_lens"]
             lens_buf.copy_(enc_lens)
             enc_lens = lens_buf
-            ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias), out=logp_ctc.view(U * T, V))
-            self.dec_step.refill(enc)
+            if has_ctc:
+                ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias), out=logp_ctc.view(U * T, V))
+            if has_dec:
+                self.dec_step.refill(enc)
             tok, yseq, score, anc, slot_ids, r_prev, s_prev, utt_base = cap["bufs"]
+            full_const = cap["full_const"]
         else:
             self._captured = None
             enc_lens = enc_lens.clone()
-            logp_ctc = ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias)).view(U, T, V)
-            self.dec_step.start(enc, enc_lens, N, K, steps)
+            logp_ctc = None
+            if has_ctc:
+                logp_ctc = ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias)).view(U, T, V)
+            if has_dec:
+                self.dec_step.start(enc, enc_lens, N, K, steps)
             if self.lm_step is not None:
                 self.lm_step.start(enc, N, steps, K)
             # running state
@@ -386,16 +513,11 @@ class BatchBeamSearch:
             score = score.view(N)
             anc = torch.zeros(N, steps, dtype=torch.int32, device=dev)
             slot_ids = torch.arange(N, dtype=torch.int32, device=dev)
-            r_prev = torch.zeros(N, T, 2, device=dev)
-            s_prev = torch.zeros(N, device=dev)
+            r_prev = torch.zeros(N, T, 2, device=dev) if has_ctc else None
+            s_prev = torch.zeros(N, device=dev) if has_ctc else None
             utt_base = (torch.arange(U, device=dev) * K).view(U, 1)
-        # host-side bookkeeping, vectorised over utterances ([U] / [N]-sized CPU tensors)
-        lens_c = torch.tensor(maxl_h)                               # per-utterance maxlen: the last iteration closes every hypothesis
-        active = torch.ones(U, dtype=torch.bool)
-        best = torch.full((U,), -float("inf"))                      # best ended score per utterance
-        best_len = torch.full((U, steps + 4), -float("inf"))        # best ended score per (utterance, hypothesis length)
-        D_end = math.log(1 * math.exp(-10))
-        NEG_INF = -float("inf")
+            # no decoder and no LM: the full scorers' row is the length bonus alone
+            full_const = torch.full((N, V), self.w_len, device=dev) if not has_dec and self.lm_step is None else None
         state = dict(r_prev=r_prev, s_prev=s_prev, yseq=yseq, score=score)
 
         def device_step(i, dyn):
@@ -419,6 +541,10 @@ class BatchBeamSearch:
             if has_lm:
                 with ops.BranchScope(enabled=SCORERS_PARALLEL) as br:
                     z_lm = self.lm_step.step(i, tok, anc, sdyn, logits_only=True)
+            # (decoder or CTC scorer absent: the twin below walks the same routes with that scorer's launches and terms left out - a
+            # change to the beam update here belongs there too; this body stays as it is so a hybrid model's launches do not move)
+            if not (has_dec and has_ctc):
+                return device_step_reduced(i, dyn, sdyn, spec, z_lm if has_lm else None, br if has_lm else None)
             if spec:
                 # on the decoder's queue, in front of its chain: the decoder has ~100 us of slack behind the LM (a third queue for it
                 # made the whole step 45 us SLOWER: profiles/r05_notes.md)
@@ -474,6 +600,86 @@ class BatchBeamSearch:
             state["yseq"], state["score"] = yseq, top_s.view(N)
             return anc[prev], new_tok
 
+        def device_step_reduced(i, dyn, sdyn, spec, z_lm, br):
+            """the step with the decoder or the CTC scorer absent (espnet drops a scorer that is None or has weight 0): the same
+            routes as above - one-launch beam update, beam_combine_topk, torch ops - with the absent scorer's launches and terms left
+            out (null operands of the beam kernels, include/tavsr.h)"""
+            r_prev, s_prev, yseq, score = state["r_prev"], state["s_prev"], state["yseq"], state["score"]
+            has_lm = z_lm is not None
+            sd = None if dyn is None else dyn["step"]
+            live = [t for t in (r_prev, s_prev) if t is not None] + [yseq, anc, tok, score]
+            shadow = None if dyn is None else [t for t in dyn["shadow"] if t is not None]
+            if spec:
+                psi = psi_abs = eos_s = eos_abs = r_new = None
+                if has_ctc:
+                    # (without pre-beam: the form that scores every token with the one-launch search's sums, bit for bit)
+                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok,
+                                                                              dyn["cand_all"] if self.pre_beam else None, K, i, step_dev=sd)
+                dec = self.dec_step.step(i, tok, anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len) if has_dec else None
+                if has_lm:
+                    br.join()
+                top_s, top_i = ops.beam_select_topk(dec, z_lm, self.w_lm, self.w_len if (has_lm or not has_dec) else 0.0, psi, psi_abs,
+                                                    eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K, C)
+                ops.beam_reorder(top_i, top_s, dyn["cand_all"], r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, sd, hist=dyn["hist"],
+                                 maxlen=dyn["maxl"], eos=self.eos)
+                ops.multi_copy_(live, shadow, inc=dyn["ctr"])
+                return anc, tok
+            if has_dec:
+                full = self.dec_step.step(i, tok, anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len)
+                if has_lm:
+                    br.join()
+                    ops.log_softmax_rows(z_lm, out=full, alpha=self.w_lm, add=self.w_len, accumulate=True)
+            elif has_lm:
+                br.join()
+                full = ops.log_softmax_rows(z_lm, alpha=self.w_lm, add=self.w_len)
+            else:
+                full = full_const
+            cand = r_new = psi = psi_abs = eos_s = eos_abs = None
+            if has_ctc:
+                if not self.pre_beam:                                  # every token is scored (ctc_weight 1, or fewer tokens than 1.5 beam)
+                    cand = dyn["cand_all"] if dyn is not None else cand_eager
+                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, None, K, i, step_dev=sd)
+                elif PREBEAM_FUSED and C <= 64 and V <= 4096:
+                    cand, r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step_topk(logp_ctc, enc_lens, r_prev, s_prev, tok, full, C, K,
+                                                                                         i, step_dev=sd)
+                else:
+                    cand = torch.topk(full, C, dim=-1)[1]
+                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, cand, K, i, step_dev=sd)
+            if dyn is not None:
+                if ops.beam_combine_topk_ok(K, V):
+                    top_s, top_i = ops.beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K)
+                else:
+                    weighted = ops.beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc)
+                    top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
+                ops.beam_reorder(top_i, top_s, cand, r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, sd, hist=dyn["hist"],
+                                 maxlen=dyn["maxl"], eos=self.eos)
+                ops.multi_copy_(live, shadow, inc=dyn["ctr"])
+                return anc, tok
+            if has_ctc:
+                is_eos_c = cand == self.eos
+                psi = torch.where(is_eos_c, eos_s.unsqueeze(1), psi)
+                psi_abs = torch.where(is_eos_c, eos_abs.unsqueeze(1), psi_abs)
+                ctc_full = torch.full((N, V), LOGZERO, device=dev) - s_prev.unsqueeze(1)
+                ctc_full[:, self.eos] = eos_s
+                ctc_full.scatter_(1, cand, psi)
+                weighted = full + self.w_ctc * ctc_full + score.unsqueeze(1)
+            else:
+                weighted = full + score.unsqueeze(1)
+            top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
+            prev = (top_i // V + utt_base).view(N)                  # slot the new hypothesis extends
+            new_tok = (top_i % V).view(N)
+            if has_ctc:                                             # CTC state of the chosen candidate
+                cidx = (cand[prev] == new_tok.unsqueeze(1)).float().argmax(dim=1)
+                state["r_prev"], state["s_prev"] = r_new[prev, :, :, cidx], psi_abs[prev, cidx]
+            yseq = yseq[prev]
+            yseq[:, i + 1] = new_tok
+            state["yseq"], state["score"] = yseq, top_s.view(N)
+            return anc[prev], new_tok
+
+        cand_eager = None
+        if has_ctc and not self.pre_beam and not (has_dec and has_ctc):
+            cand_eager = torch.arange(V, dtype=torch.int64, device=dev).repeat(N, 1)
+
         def reset_state():
             tok.fill_(self.sos)
             yseq.fill_(self.eos)
@@ -482,8 +688,9 @@ class BatchBeamSearch:
             score.view(U, K)[:, 0] = 0.0
             anc.zero_()
             anc[:, 0] = slot_ids                                      # step 0's own key / value rows
-            r_prev.zero_()
-            s_prev.zero_()
+            if has_ctc:
+                r_prev.zero_()
+                s_prev.zero_()
 
         graph = dyn = None
         if cap is not None:
@@ -506,8 +713,10 @@ class BatchBeamSearch:
                        maxl=torch.tensor(maxl_h, dtype=torch.int32, device=dev),
                        hist=torch.zeros(steps, 3, N, dtype=torch.int32, device=dev),
                        cand_all=torch.arange(V, dtype=torch.int64, device=dev).repeat(N, 1),      # every token a "candidate" of the CTC scorer
-                       shadow=(torch.empty_like(r_prev), torch.empty_like(s_prev), torch.empty_like(yseq), torch.empty_like(anc),
-                               torch.empty_like(tok), torch.empty_like(score)))
+                       shadow=(torch.empty_like(r_prev) if has_ctc else None, torch.empty_like(s_prev) if has_ctc else None,
+                               torch.empty_like(yseq), torch.empty_like(anc), torch.empty_like(tok), torch.empty_like(score)))
+            if not has_ctc:
+                dyn["cand_all"] = None
             side = torch.cuda.Stream()
             side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(side):
@@ -519,41 +728,7 @@ class BatchBeamSearch:
             with torch.cuda.graph(graph):
                 device_step(steps, dyn)
             self._captured = dict(key=key, graph=graph, dyn=dyn, logp_ctc=logp_ctc, enc_lens=enc_lens,
-                                  bufs=(tok, yseq, score, anc, slot_ids, r_prev, s_prev, utt_base))
-        ended = [[] for _ in range(U)]
-
-        def host_step(i, tok_h, score_h, rows_of):
-            """espnet post_process / end_detect for token i of every utterance: collects the hypotheses that end here
-            (``rows_of(slot indices)`` -> their token lists incl. <sos>), returns the slots to retire."""
-            nonlocal active
-            valid = torch.isfinite(score_h).view(U, K) & active.view(U, 1)
-            last = (lens_c - 1 == i).view(U, 1)
-            # espnet appends <eos> to EVERY hypothesis of the last iteration (also to the ones that just ended)
-            take = valid & ((tok_h.view(U, K) == self.eos) | last)
-            if bool(take.any()):
-                idx = take.view(N).nonzero().view(-1)
-                us = idx // K
-                lns = torch.where(last.view(U)[us], torch.full_like(us, i + 3), torch.full_like(us, i + 2))
-                scs = score_h[idx]
-                for ys, u_, ln, sc in zip(rows_of(idx), us.tolist(), lns.tolist(), scs.tolist()):
-                    ys = (ys + [self.eos] * 2)[:ln]
-                    ys[ln - 1] = self.eos
-                    ended[u_].append((ys, sc))
-                best.index_reduce_(0, us, scs, "amax")
-                flat = us * best_len.shape[1] + lns
-                best_len.view(-1).index_reduce_(0, flat, scs, "amax")
-            running = (valid & ~take).sum(dim=1)
-            count = torch.zeros(U, dtype=torch.int64)
-            for m in range(3):                                     # end_detect: M = 3 most recent lengths
-                if i - m >= 0:
-                    bl = best_len[:, i - m]
-                    count += (torch.isfinite(bl) & (bl - best < D_end)).to(torch.int64)
-            if self.maxlenratio != 0.0:                            # end_detect runs only for maxlenratio == 0
-                count.zero_()
-            stop = (count == 3) | (running == 0) | last.view(U)
-            active = active & ~stop
-            return (take | ~active.view(U, 1)).view(N)
-
+                                  bufs=(tok, yseq, score, anc, slot_ids, r_prev, s_prev, utt_base), full_const=full_const)
         if graph is not None:
             hist = dyn["hist"]
             need = steps * 3 * N                                    # page-locked landing zone of the records: ONE buffer that
@@ -561,18 +736,6 @@ class BatchBeamSearch:
                 self._pinned = torch.empty(max(need, 1 << 16), dtype=torch.int32, pin_memory=True)
             pin = self._pinned[:need].view(steps, 3, N)
             rec = pin.numpy()                                       # same memory: rec[token][0 / 1 / 2][slot]
-
-            def rows_from_records(i):
-                def rows_of(idx):
-                    out_rows = []
-                    for n in idx.tolist():
-                        toks, cur = [], n
-                        for t in range(i, -1, -1):                  # back-track: token of slot `cur`, then the slot it extended
-                            toks.append(int(rec[t, 0, cur]))
-                            cur = int(rec[t, 1, cur])
-                        out_rows.append([self.sos] + toks[::-1])
-                    return out_rows
-                return rows_of
 
             events, done = [], 0
             timing = os.environ.get("TAVSR_DECODE_TIMING") == "1"   # host-side cost of a token: replay call / record processing
@@ -627,11 +790,7 @@ class BatchBeamSearch:
                     state["score"] = torch.where(kill.to(dev), torch.full_like(score, NEG_INF), score)
                 if not bool(active.any()):
                     break
-        out = []
-        for u in range(U):
-            hyps = sorted(ended[u], key=lambda h: h[1], reverse=True)
-            out.append(hyps if nbest is None else hyps[:nbest])
-        return out
+        return nbest_lists()
 
 
 class CapturedEncode:
@@ -674,11 +833,13 @@ class Speech2Text:
     the reference returns them (:492-518): (text, tokens, token ids without sos/eos/blank, (yseq, score))."""
 
     def __init__(self, asr_model, lm=None, beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
-                 penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0):
+                 penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0,
+                 skip_zero_weight: bool = False):
         self.asr_model = asr_model.eval()
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
-        self.beam_search = BatchBeamSearch(asr_model, lm, beam_size, ctc_weight, lm_weight, penalty, maxlenratio, minlenratio)
+        self.beam_search = BatchBeamSearch(asr_model, lm, beam_size, ctc_weight, lm_weight, penalty, maxlenratio, minlenratio,
+                                           skip_zero_weight=skip_zero_weight)
         self.encode = CapturedEncode(self.asr_model)
 
     @torch.no_grad()

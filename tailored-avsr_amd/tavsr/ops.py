@@ -2004,9 +2004,10 @@ def kv_append(k, v, kpool, vpool, N, max_steps, step_dev):
 
 def ctc_prefix_step(logp, lens, r_prev, s_prev, last_tok, cand, K, out_len, blank=0, step_dev=None):
     """-> (r_new [N,T,2,C], psi [N,C], psi_abs [N,C], eos [N], eos_abs [N]); see include/tavsr.h.
-    ``step_dev`` (int32 device scalar) replaces ``out_len`` (graph replays)."""
+    ``step_dev`` (int32 device scalar) replaces ``out_len`` (graph replays).  ``cand`` None: every token is scored (C = V), with the
+    sums of the one-launch search (``ctc_beam_search``), bit for bit."""
     U, T, V = logp.shape
-    N, Cn = cand.shape
+    N, Cn = (s_prev.shape[0], V) if cand is None else cand.shape
     require_cuda(logp, lens, r_prev, s_prev, last_tok, cand)
     r_new = empty(N, T, 2, Cn, like=logp)
     psi, psi_abs = empty(N, Cn, like=logp), empty(N, Cn, like=logp)
@@ -2057,9 +2058,10 @@ def log_softmax_rows(x, V=None, out=None, alpha=1.0, add=0.0, accumulate=False):
 
 
 def beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, eos, w_ctc):
-    """weighted = full + w_ctc * (partial CTC scorer row) + score; fixes psi_abs of <eos> candidates in place (tavsr.h)."""
+    """weighted = full + w_ctc * (partial CTC scorer row) + score; fixes psi_abs of <eos> candidates in place (tavsr.h).
+    ``psi`` None: no CTC scorer - weighted = full + score, the other CTC operands are not read."""
     N, V = full.shape
-    Cn = cand.shape[1]
+    Cn = 0 if psi is None else cand.shape[1]
     require_cuda(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score)
     weighted = empty(N, V, like=full)
     check(lib().tavsr_beam_combine(ptr(full), ptr(cand), ptr(psi), ptr(psi_abs), ptr(eos_s), ptr(eos_abs), ptr(s_prev), ptr(score),
@@ -2072,9 +2074,10 @@ def beam_combine_topk_ok(K, V) -> bool:
 
 
 def beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, eos, w_ctc, K, keep_weighted=False):
-    """``beam_combine`` and ``torch.topk(weighted.view(U, K * V), K)`` in one launch -> (top_s, top_i[, weighted])."""
+    """``beam_combine`` and ``torch.topk(weighted.view(U, K * V), K)`` in one launch -> (top_s, top_i[, weighted]).
+    ``psi`` None: no CTC scorer (weighted = full + score)."""
     N, V = full.shape
-    Cn = cand.shape[1]
+    Cn = 0 if psi is None else cand.shape[1]
     require_cuda(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score)
     top_s = empty(N // K, K, like=full)
     top_i = torch.empty(N // K, K, dtype=torch.int64, device=full.device)
@@ -2091,15 +2094,18 @@ def beam_select_topk_ok(K, V) -> bool:
 
 def beam_select_topk(dec, z_lm, w_lm, add, psi_all, psi_abs_all, eos_s, eos_abs, s_prev, score, eos, w_ctc, K, Cn, keep=False):
     """the beam update behind the scorers in one launch (tavsr_beam_select_topk; V <= 64): -> (top_s, top_i) or, with ``keep``,
-    (top_s, top_i, full, weighted, cand) - the intermediate values the separate launches would have produced"""
-    N, V = dec.shape
+    (top_s, top_i, full, weighted, cand) - the intermediate values the separate launches would have produced.
+    ``dec`` None: no decoder term (the row is w_lm * log_softmax(z_lm) + add, or ``add`` alone); ``psi_all`` None: no CTC scorer
+    (no pre-beam, weighted = full + score; ``cand`` is then not produced)."""
+    like = next(t for t in (dec, z_lm, psi_all) if t is not None)
+    N, V = like.shape
     require_cuda(dec, z_lm, psi_all, psi_abs_all, eos_s, eos_abs, s_prev, score)
-    assert dec.is_contiguous() and psi_all.is_contiguous() and psi_abs_all.is_contiguous() and (z_lm is None or z_lm.is_contiguous())
-    top_s = empty(N // K, K, like=dec)
-    top_i = torch.empty(N // K, K, dtype=torch.int64, device=dec.device)
-    full = empty(N, V, like=dec) if keep else None
-    weighted = empty(N, V, like=dec) if keep else None
-    cand = torch.empty(N, Cn, dtype=torch.int64, device=dec.device) if keep else None
+    assert all(t is None or t.is_contiguous() for t in (dec, z_lm, psi_all, psi_abs_all))
+    top_s = empty(N // K, K, like=like)
+    top_i = torch.empty(N // K, K, dtype=torch.int64, device=like.device)
+    full = empty(N, V, like=like) if keep else None
+    weighted = empty(N, V, like=like) if keep else None
+    cand = torch.empty(N, Cn, dtype=torch.int64, device=like.device) if keep and psi_all is not None else None
     check(lib().tavsr_beam_select_topk(ptr(dec), ptr(z_lm), w_lm, add, ptr(psi_all), ptr(psi_abs_all), ptr(eos_s), ptr(eos_abs),
                                        ptr(s_prev), ptr(score), ptr(full), ptr(weighted), ptr(cand), ptr(top_s), ptr(top_i), N, K, V,
                                        int(Cn), int(eos), w_ctc, stream()), "tavsr_beam_select_topk")
@@ -2117,14 +2123,18 @@ def beam_step_begin(score, tok, anc, maxlen, K, eos, step_dev):
 
 def beam_reorder(top_i, top_s, cand, r_new, psi_abs, yseq, anc, outs, K, V, step_dev, hist=None, maxlen=None, eos=0):
     """gathers the state of the extended slots into ``outs`` = (r, s, yseq, anc, tok, score) buffers (tavsr.h).  ``maxlen`` (int32
-    [N / K]): the head of the next step rides along (tavsr_beam_reorder_begin)."""
-    N, Cn = cand.shape
-    T = r_new.shape[1]
+    [N / K]): the head of the next step rides along (tavsr_beam_reorder_begin).  ``r_new`` None: no CTC state to gather -
+    ``cand`` / ``psi_abs`` and the first two of ``outs`` are not used (may be None)."""
+    N = yseq.shape[0]
+    Cn, T = (0, 0) if r_new is None else (cand.shape[1], r_new.shape[1])
     r_out, s_out, y_out, a_out, t_out, sc_out = outs
-    require_cuda(top_i, top_s, cand, r_new, psi_abs, yseq, anc, *outs, step_dev, hist)
+    if r_new is None:
+        cand = psi_abs = r_out = s_out = None
+    require_cuda(top_i, top_s, cand, r_new, psi_abs, yseq, anc, r_out, s_out, y_out, a_out, t_out, sc_out, step_dev, hist)
     assert hist is None or (hist.dtype == torch.int32 and hist.is_contiguous() and hist.shape[1:] == (3, N))
     assert top_i.is_contiguous() and top_s.is_contiguous() and top_i.numel() == N and yseq.dtype == torch.int64
-    assert anc.dtype == torch.int32 and y_out.shape == yseq.shape and a_out.shape == anc.shape and r_out.shape == (N, T, 2)
+    assert anc.dtype == torch.int32 and y_out.shape == yseq.shape and a_out.shape == anc.shape
+    assert r_new is None or (cand.shape[0] == N and r_out.shape == (N, T, 2))
     if maxlen is not None:
         require_cuda(maxlen)
         assert maxlen.dtype == torch.int32 and maxlen.numel() == N // K
@@ -2137,6 +2147,26 @@ def beam_reorder(top_i, top_s, cand, r_new, psi_abs, yseq, anc, outs, K, V, step
                                    ptr(s_out), ptr(y_out), ptr(a_out), ptr(t_out), ptr(sc_out), N, K, V, Cn, T, yseq.stride(0),
                                    anc.stride(0), ptr(step_dev), ptr(hist), 0 if hist is None else hist.shape[0], stream()),
           "tavsr_beam_reorder")
+
+
+def ctc_beam_search_ok(K, V, T) -> bool:
+    """does the one-launch CTC prefix beam search take this (beam, vocabulary, frames)?  K <= V <= 64 and the beam's forward
+    variables (16 K T bytes, two LDS buffers) plus a few KB within one workgroup's 160 KiB - the library's answer."""
+    return bool(lib().tavsr_ctc_beam_search_ok(int(K), int(V), int(T)))
+
+
+def ctc_beam_search(logp, lens, maxlen, hist, n_steps, K, sos, eos, w_ctc, add, end_detect, d_end, blank=0):
+    """the whole CTC prefix beam search (scorers: CTC prefix scorer + length bonus, no pre-beam) of every utterance in one launch
+    (tavsr_ctc_beam_search): logp [U, T, V], lens int64 [U], maxlen int32 [U] -> records in ``hist`` int32 [steps, 3, U * K] and
+    the number of tokens searched per utterance in ``n_steps`` int32 [U]."""
+    U, T, V = logp.shape
+    require_cuda(logp, lens, maxlen, hist, n_steps)
+    assert logp.is_contiguous() and logp.dtype == f32 and lens.dtype == torch.int64 and lens.numel() == U
+    assert maxlen.dtype == torch.int32 and maxlen.numel() == U and n_steps.dtype == torch.int32 and n_steps.numel() == U
+    assert hist.dtype == torch.int32 and hist.is_contiguous() and hist.shape[1:] == (3, U * K)
+    check(lib().tavsr_ctc_beam_search(ptr(logp), ptr(lens), ptr(maxlen), ptr(hist), ptr(n_steps), U, int(K), T, V, hist.shape[0],
+                                      int(sos), int(eos), int(blank), w_ctc, add, int(bool(end_detect)), d_end, stream()),
+          "tavsr_ctc_beam_search")
 
 
 # ---------------------------------------------------------------------------------------------- dropout
