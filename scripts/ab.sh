@@ -1,5 +1,6 @@
 # A/B inside ONE session on one GPU (GPUs of one pool differ by 1 - 2 %): bench.py under each environment given, twice, alternating.
 # usage: bash scripts/ab.sh asr "TAVSR_WGRAD_BESIDE=0" "TAVSR_WGRAD_BESIDE=1" ...   (files under $OUT_DIR, default bench_out/)
+#        bash scripts/ab.sh avsr "TAVSR_LIB=$PWD/lib_b/libtavsr_hip.so" "TAVSR_LIB=$PWD/tailored-avsr_amd/tavsr/lib/libtavsr_hip.so"   (two builds of the library)
 OUT_DIR=${OUT_DIR:-bench_out}
 mkdir -p "$OUT_DIR"
 W=$1; shift

@@ -1660,14 +1660,14 @@ def conv_wflip(w2d, cout, cin):
 CONV_TAPSKIP = os.environ.get("TAVSR_CONV_TAPSKIP", "1") != "0"
 CONV_TAPSKIP_MAXPOS = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS", "121"))
 # Tile order of the position-major forward / data gradient launches: tiles sorted by tap count and dealt evenly to the XCDs
-# (csrc/gemm.hip, struct TileOrder; bit-identical results).  TAVSR_CONV_TILEORDER=0: one contiguous range of tiles per XCD, as
+# (csrc/gemm_conv.hip, struct TileOrder; bit-identical results).  TAVSR_CONV_TILEORDER=0: one contiguous range of tiles per XCD, as
 # before (A/B switch; bit 1 of conv_posmajor).
 CONV_TILEORDER = os.environ.get("TAVSR_CONV_TILEORDER", "1") != "0"
 # The weight gradient has a gate of its own: its position-major walk costs bookkeeping per K-step that the forward does not
 # pay, so a map can gain in one direction and lose in the other: the 11x11 map's weight gradient is 4 % SLOWER with the skip
 # (profiles/r08_notes.md has the per-shape rows behind both gates) and stays outside.
 CONV_TAPSKIP_MAXPOS_DW = int(os.environ.get("TAVSR_CONV_TAPSKIP_MAXPOS_DW", "36"))
-# K slices of two lengths for the position-major weight gradient where equal slices leave block slots empty (csrc/gemm.hip,
+# K slices of two lengths for the position-major weight gradient where equal slices leave block slots empty (csrc/gemm_conv.hip,
 # plan_conv: trunk layer 3 at 3200 frames, 32 slices instead of 24; another summation order).  TAVSR_CONV_DW_UNEVEN=0: equal
 # slices, as before (A/B switch; bit 2 of conv_posmajor).
 CONV_DW_UNEVEN = os.environ.get("TAVSR_CONV_DW_UNEVEN", "1") != "0"

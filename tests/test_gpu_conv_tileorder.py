@@ -1,4 +1,4 @@
-"""Tile order of the position-major 3x3 forward / data-gradient launches (csrc/gemm.hip, struct TileOrder; ops.CONV_TILEORDER):
+"""Tile order of the position-major 3x3 forward / data-gradient launches (csrc/gemm_conv.hip, struct TileOrder; ops.CONV_TILEORDER):
 the tiles are sorted by tap count and dealt to the 8 XCDs in rounds, instead of one contiguous range of tiles per XCD.
 
 * The order is a pure function of the grid: ``tavsr_conv_tile_order`` evaluates the kernel's own ``tile_order_map`` on the host.

@@ -1,4 +1,4 @@
-"""Trunk convolutions, round 8 (csrc/gemm.hip, plan_conv / dw_xcd_order; ops.CONV_DW_UNEVEN, ops.CONV_TAPSKIP_MAXPOS_DW).
+"""Trunk convolutions, round 8 (csrc/gemm_conv.hip, plan_conv / dw_xcd_order; ops.CONV_DW_UNEVEN, ops.CONV_TAPSKIP_MAXPOS_DW).
 
 * K slices of two lengths for the position-major weight gradient: where equal slices of whole lcm(H*W, 32)-pixel units leave
   block slots empty, the first ``n_big`` of a multiple of 8 slices are one unit longer than the rest (layer 3 at 3200 frames:

@@ -282,3 +282,43 @@ def test_gemm_ln_result_and_its_layernorm_from_the_launch_that_finishes_the_rows
     assert float((n.double() - nref).abs().max() / nref.abs().max()) < 5e-6
     n0 = ops.layernorm_fwd(y0, gam, bet, 1e-12, save=False)[0]
     assert float((n - n0).abs().max() / n0.abs().max()) < 2e-6
+
+
+@pytest.mark.parametrize("cfg", [0, 1, 2, 3, 4, 5, 6, 7, 8])
+def test_gemm_every_tile_config_on_the_tt_layout(cfg):
+    """the fourth layout (A [K, M], B [N, K]) of every LDS-DMA tile configuration, forced, with ragged edges and a forced
+    K split: no caller of the package uses it, the C ABI offers it"""
+    from tavsr import ops
+    torch.manual_seed(cfg)
+    M, N, K = 300, 200, 416
+    a, b = torch.randn(M, K, device="cuda"), torch.randn(K, N, device="cuda")
+    A, B = a.t().contiguous(), b.t().contiguous()
+    ref = a.double() @ b.double()
+    for ns in (1, 3):
+        out = torch.zeros(M, N, device="cuda")
+        ops.gemm(M, N, K, A, M, B, K, out, N, a_kmajor=True, b_kmajor=False, force=(cfg, ns))
+        assert (out.double() - ref).abs().max() / ref.abs().max() < 2e-6, (cfg, ns)
+
+
+@pytest.mark.parametrize("mode", ["NT", "NN", "TN", "TT"])
+def test_gemm_grouped_launch_on_every_layout(mode):
+    """tavsr_gemm_grouped: two problems of one layout (ragged rows, different N and K) in one grid, with bias"""
+    from tavsr import _lib as L
+    torch.manual_seed(len(mode) + ord(mode[0]) + ord(mode[1]))
+    a_km, b_km = mode[0] == "T", mode[1] == "N"
+    arr = (L.GemmDesc * 2)()
+    keep, want = [], []
+    for d, (M, N, K) in zip(arr, ((100, 64, 96), (132, 200, 64))):
+        a, b, bias = torch.randn(M, K, device="cuda"), torch.randn(K, N, device="cuda"), torch.randn(N, device="cuda")
+        A = a.t().contiguous() if a_km else a
+        B = b if b_km else b.t().contiguous()
+        out = torch.zeros(M, N, device="cuda")
+        d.M, d.N, d.K, d.a_kmajor, d.b_kmajor = M, N, K, int(a_km), int(b_km)
+        d.A, d.lda, d.B, d.ldb, d.C, d.ldc = A.data_ptr(), A.stride(0), B.data_ptr(), B.stride(0), out.data_ptr(), N
+        d.nb1 = d.nb2 = 1
+        d.bias, d.alpha = bias.data_ptr(), 1.0
+        keep += [A, B, bias]
+        want.append((out, a.double() @ b.double() + bias.double()))
+    L.check(L.lib().tavsr_gemm_grouped(arr, 2, L.stream()), "tavsr_gemm_grouped")
+    for out, ref in want:
+        assert (out.double() - ref).abs().max() / ref.abs().max() < 2e-6, mode
