@@ -86,7 +86,7 @@ def measure(dev, encode, routes, B, reps, lines, rec):
                     tokens[name].append(max(search.n_steps))
             assert outs[ROUTES[1]] == outs[ROUTES[2]], "the stepwise and the one-launch CTC search disagree"
             same_as_hybrid &= [[h[0] for h in u] for u in outs[ROUTES[0]]] == [[h[0] for h in u] for u in outs[ROUTES[2]]]
-    assert routes[1][1]._captured["graph"] is not None and routes[2][1]._captured["graph"] is None      # the routes really taken
+    assert routes[1][1]._captured.graph is not None and routes[2][1]._captured.graph is None      # the routes really taken
     lines.append(f"batch {B}: {reps} timed rounds; (ii) and (iii) return identical hypotheses and scores, (i) the same best token sequences: "
                  f"{'yes' if same_as_hybrid else 'NO'}")
     lines.append(f"  {'route':<22} {'ms / decode p50':>16} {'p10':>9} {'p90':>9} {'tokens':>8} {'us / token':>11} {'utt / s':>10}")
@@ -105,17 +105,17 @@ def measure(dev, encode, routes, B, reps, lines, rec):
     # decode() call is the CTC head's GEMM + log-softmax, two device-to-host copies and the host's per-token replay of the records)
     from tavsr import ops
     search = routes[2][1]
-    cap = search._captured
+    cap = search._captured.bufs
     ms = []
     for _ in range(7):
         t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0.record()
-        ops.ctc_beam_search(cap["logp_ctc"], cap["enc_lens"], cap["maxl"], cap["hist"], cap["n_steps"], BEAM, search.sos, search.eos,
+        ops.ctc_beam_search(cap.logp_ctc, cap.enc_lens, cap.maxl, cap.hist, cap.n_steps, BEAM, search.sos, search.eos,
                             search.w_ctc, search.w_len, True, -10.0)
         t1.record()
         torch.cuda.synchronize()
         ms.append(t0.elapsed_time(t1))
-    dev_ms, ntok = float(np.median(ms[1:])), int(cap["n_steps"].max())
+    dev_ms, ntok = float(np.median(ms[1:])), int(cap.n_steps.max())
     lines.append(f"  the one launch alone (device events): {dev_ms:.3f} ms for {ntok} tokens = {1e3 * dev_ms / ntok:.1f} us / token")
     r["launch_ms"], r["launch_us_per_token"] = round(dev_ms, 3), round(1e3 * dev_ms / ntok, 1)
 

@@ -11,8 +11,8 @@ advance together (the reference decodes one utterance at a time on the CPU):
   and values stay where they were written; a hypothesis is an int32 list of ancestor rows), source attention against
   the per-utterance memory keys/values projected once, CTC prefix scores of the pre-beam candidates by
   ``tavsr_ctc_prefix_step``.
-* The per-step bookkeeping (top-k, ancestor-list gathers, ended-hypothesis lists, end detection) is torch / host code:
-  index plumbing on [N]-sized tensors.
+* The per-step bookkeeping is index plumbing on [N]-sized tensors: top-k and ancestor-list gathers in the beam-update launches,
+  ended-hypothesis lists and end detection on the host (inference/search_host.py).
 
 * The scorer set is espnet's: a scorer that is None or has weight 0 drops out (a model without decoder: CTC prefix beam search, with
   or without LM; a model without CTC head: attention beam search).  Scorers {ctc, length_bonus} without pre-beam are searched in ONE
@@ -25,15 +25,16 @@ from __future__ import annotations
 
 import math
 import os
+import time
 from typing import Optional
 
 import torch
 
 from .. import ops
+from .search_host import D_END, HostSearch
 
 EPS = 1e-12
 LOGZERO = -10000000000.0
-GRAPH_STEP = os.environ.get("TAVSR_DECODE_GRAPH", "1") != "0"      # capture the scorer step into one hipGraph
 
 
 def _cat(ws):
@@ -44,24 +45,20 @@ class _DerivedWeights:
     """The step objects keep a few DERIVED copies of parameters (q / k / v weights side by side for one launch, the LM's input
     table).  Everything else is read through the parameters' own storage.  ``sync()`` re-derives the copies IN PLACE (captured
     graphs keep reading the same buffers) when a source parameter's version counter has moved since they were made - an
-    optimizer step or ``load_state_dict`` between two decodes (validation while training)."""
+    optimizer step or ``load_state_dict`` after the search object was built or between two decodes (validation while training)."""
 
     def __init__(self):
         self._derived = []          # (destination, source parameters)
-        self._seen = None
+        self._seen = ()             # the sources' versions when the copies were made / last re-derived
 
     def cat(self, ws):
         dst = _cat(ws)
         self._derived.append((dst, list(ws)))
+        self._seen += tuple(w._version for w in ws)
         return dst
 
-    def _versions(self):
-        return tuple(w._version for _, ws in self._derived for w in ws)
-
     def sync(self) -> bool:
-        now = self._versions()
-        if self._seen is None:
-            self._seen = now
+        now = tuple(w._version for _, ws in self._derived for w in ws)
         if now == self._seen:
             return False
         for dst, ws in self._derived:
@@ -70,22 +67,26 @@ class _DerivedWeights:
         return True
 
 
-# One-token scorer steps are chains of small launches: the fused feed-forward block (LayerNorm + both GEMMs, csrc/ffn.hip)
-# and the fused source attention cut the chain.  TAVSR_DECODE_FUSED=0 keeps the GEMM launches (A/B switch).
+# Route constants: module attributes read at call time (tests and scripts/decode_chain_probe.py flip them in-process); the two that
+# name an environment variable take their default from it.
+# the scorer step as one hipGraph, captured once per batch shape and replayed per token; False: eager launches, host in the loop
+GRAPH_STEP = os.environ.get("TAVSR_DECODE_GRAPH", "1") != "0"
+# the decoder's source attention (scores, mask, softmax, context) as one launch (csrc/attn_fused.hip); False: two GEMMs and a softmax
 FUSED_STEP = True
-SCORERS_PARALLEL = True   # decoder || LM on two streams (TAVSR_SINGLE_STREAM=1 disables every fork)
-TREE_GROUP = 1     # beams of an utterance side by side in the tree attention
-PREBEAM_FUSED = True   # pre-beam top-k inside the CTC prefix launch
-# Vocabularies of up to 64 tokens (character models): the CTC prefix scores of EVERY token are computed beside the LM's chain, in front
-# of the decoder's - the recursion over the frames (20 us) leaves the critical path of a captured step - and the whole beam update
-# behind the scorers (LM log-softmax, pre-beam, weighted scores, top-k) is one launch (tavsr_beam_select_topk).
-# (module constants, flipped in-process by tests/test_beam_search.py and scripts/decode_chain_probe.py - not environment switches)
+SCORERS_PARALLEL = True   # the LM's chain on a side queue beside the decoder's (TAVSR_SINGLE_STREAM=1 disables every fork)
+TREE_GROUP = 1            # tree attention: beams of an utterance side by side, in groups of TREE_GROUP * beam rows
+# pre-beam top-k on the weighted full scores inside the CTC prefix launch (tavsr_ctc_prefix_step_topk; up to 64 candidates of up to
+# 4096 tokens); False: torch.topk, then tavsr_ctc_prefix_step on its candidates
+PREBEAM_FUSED = True
 # per-token records on a queue of their own (TAVSR_RECORD_QUEUE=1) or on the search queue between two replays (default).  A queue of their
 # own needs an event behind every replay that ANOTHER queue waits on - and that wait costs the NEXT replay ~1.5 us per launch it holds
 # (scripts/graph_pair_probe.py: 60 launches +90 us, 190 launches +275 us; an event record alone, an eager launch or the 128-byte copy on
 # the replaying queue itself: +5 us).  In the search: 633 -> 563 us per token at batch 1, 2359 -> 2188 at batch 64 (same process, alternating).
 RECORD_QUEUE = os.environ.get("TAVSR_RECORD_QUEUE", "0") == "1"
-LN_IN_EPILOGUE = True      # batched steps: tavsr_gemm_ln at the x + f(x) -> norm(x) seams
+LN_IN_EPILOGUE = True     # more than 32 rows: tavsr_gemm_ln at the x + f(x) -> norm(x) seams; False: a LayerNorm launch of its own
+# Vocabularies of up to 64 tokens (character models), captured step: the CTC prefix scores of EVERY token are computed beside the LM's
+# chain, in front of the decoder's - the recursion over the frames (20 us) leaves the critical path - and the whole beam update behind
+# the scorers (LM log-softmax, pre-beam, weighted scores, top-k) is one launch (tavsr_beam_select_topk); False: CTC behind the scorers
 CTC_BESIDE_SCORERS = True
 # A CTC-only search without LM (scorers {ctc, length_bonus}, no pre-beam) has no neural chain per token: the whole search of an
 # utterance is ONE launch, the beam's forward variables resident in LDS (tavsr_ctc_beam_search), where its shape fits
@@ -360,437 +361,386 @@ class BatchBeamSearch:
         """names of the scorers the search runs (espnet's keys)"""
         return tuple(k for k, on in (("decoder", self.has_dec), ("ctc", self.has_ctc), ("length_bonus", True), ("lm", self.has_lm)) if on)
 
+    @property
+    def _ctc_all_tokens(self):
+        """The one real difference between a hybrid model's step and the step with the decoder absent, where there is NO pre-beam:
+        without decoder the CTC launch gets no candidate list (``cand=None``) and scores every token with explicit fma sums, bit-equal
+        to the one-launch search.  A hybrid model without pre-beam (ctc_weight 1.0 without ``skip_zero_weight``, or int(1.5 beam) >= V)
+        keeps handing the launch a candidate list - every token, or its top-C row - whose sums are the source-expression form.
+        Unifying the two would move bits for hybrid models."""
+        return self.has_ctc and not self.has_dec and not self.pre_beam
+
+    def _ctc_logp(self, enc, out=None):
+        """log-softmax of the CTC head over every frame [U, T, V] (``out``: into a captured step's buffer)"""
+        U, T, D = enc.shape
+        ctc = self.model.ctc
+        z = ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias)
+        return ops.log_softmax_rows(z, out=None if out is None else out.view(U * T, self.V)).view(U, T, self.V)
+
     @torch.no_grad()
     def decode(self, enc: torch.Tensor, enc_lens: torch.Tensor, nbest: Optional[int] = None):
         """enc [U, T, D] encoder outputs, enc_lens [U] -> per utterance [(yseq list incl. sos/eos, score), ...] sorted."""
         U, T, D = enc.shape
-        K, V, C = self.K, self.V, self.C
-        N = U * K
         dev = enc.device
         enc = enc.contiguous().float()
         enc_lens = enc_lens.to(dev).to(torch.int64)
         lens_h = [int(v) for v in enc_lens.cpu()]
-        if self.maxlenratio == 0.0:                                # at most T tokens per utterance, end detection below
-            maxl_h = list(lens_h)
-        elif self.maxlenratio < 0:
-            maxl_h = [-1 * int(self.maxlenratio)] * U
-        else:
-            maxl_h = [max(1, int(self.maxlenratio * t)) for t in lens_h]
-        has_dec, has_ctc = self.has_dec, self.has_ctc
-        if has_ctc and any(m > t for m, t in zip(maxl_h, lens_h)):
+        host = HostSearch(self.maxlenratio, lens_h, self.K, self.sos, self.eos)
+        if self.has_ctc and any(m > t for m, t in zip(host.maxl, lens_h)):
             # espnet's CTCPrefixScoreTH indexes its forward variables by output length: a hypothesis longer than the number
             # of frames raises IndexError there; refused up front here
             raise ValueError(f"maxlenratio {self.maxlenratio} asks for more tokens than encoder frames {lens_h}: "
                              "the CTC prefix scorer cannot score a prefix longer than its input")
-        steps = max(maxl_h)
-        ctc = self.model.ctc
-        # derived weight copies follow the parameters (an optimizer step / load_state_dict since the last call): ADVICE round 4
-        if has_dec:
+        # derived weight copies follow the parameters (an optimizer step / load_state_dict since they were made): ADVICE rounds 4, 5
+        if self.has_dec:
             self.dec_step.weights.sync()
-        if self.lm_step is not None:
+        if self.has_lm:
             self.lm_step.sync_weights()
         # scorers {ctc, length_bonus} without pre-beam: the whole search is one launch where the beam's lattice fits a workgroup's LDS
-        fused = has_ctc and not has_dec and self.lm_step is None and not self.pre_beam and CTC_SEARCH_FUSED and ops.ctc_beam_search_ok(K, V, T)
-        # host-side bookkeeping, vectorised over utterances ([U] / [N]-sized CPU tensors)
-        lens_c = torch.tensor(maxl_h)                               # per-utterance maxlen: the last iteration closes every hypothesis
-        active = torch.ones(U, dtype=torch.bool)
-        n_host = torch.zeros(U, dtype=torch.int32)                  # tokens searched per utterance
-        best = torch.full((U,), -float("inf"))                      # best ended score per utterance
-        best_len = torch.full((U, steps + 4), -float("inf"))        # best ended score per (utterance, hypothesis length)
-        D_end = math.log(1 * math.exp(-10))
-        NEG_INF = -float("inf")
-        ended = [[] for _ in range(U)]
-
-        def host_step(i, tok_h, score_h, rows_of):
-            """espnet post_process / end_detect for token i of every utterance: collects the hypotheses that end here
-            (``rows_of(slot indices)`` -> their token lists incl. <sos>), returns the slots to retire."""
-            nonlocal active
-            n_host.add_(active.to(torch.int32))
-            valid = torch.isfinite(score_h).view(U, K) & active.view(U, 1)
-            last = (lens_c - 1 == i).view(U, 1)
-            # espnet appends <eos> to EVERY hypothesis of the last iteration (also to the ones that just ended)
-            take = valid & ((tok_h.view(U, K) == self.eos) | last)
-            if bool(take.any()):
-                idx = take.view(N).nonzero().view(-1)
-                us = idx // K
-                lns = torch.where(last.view(U)[us], torch.full_like(us, i + 3), torch.full_like(us, i + 2))
-                scs = score_h[idx]
-                for ys, u_, ln, sc in zip(rows_of(idx), us.tolist(), lns.tolist(), scs.tolist()):
-                    ys = (ys + [self.eos] * 2)[:ln]
-                    ys[ln - 1] = self.eos
-                    ended[u_].append((ys, sc))
-                best.index_reduce_(0, us, scs, "amax")
-                flat = us * best_len.shape[1] + lns
-                best_len.view(-1).index_reduce_(0, flat, scs, "amax")
-            running = (valid & ~take).sum(dim=1)
-            count = torch.zeros(U, dtype=torch.int64)
-            for m in range(3):                                     # end_detect: M = 3 most recent lengths
-                if i - m >= 0:
-                    bl = best_len[:, i - m]
-                    count += (torch.isfinite(bl) & (bl - best < D_end)).to(torch.int64)
-            if self.maxlenratio != 0.0:                            # end_detect runs only for maxlenratio == 0
-                count.zero_()
-            stop = (count == 3) | (running == 0) | last.view(U)
-            active = active & ~stop
-            return (take | ~active.view(U, 1)).view(N)
-
-        def rows_from_records(i):
-            def rows_of(idx):
-                out_rows = []
-                for n in idx.tolist():
-                    toks, cur = [], n
-                    for t in range(i, -1, -1):                  # back-track: token of slot `cur`, then the slot it extended
-                        toks.append(int(rec[t, 0, cur]))
-                        cur = int(rec[t, 1, cur])
-                    out_rows.append([self.sos] + toks[::-1])
-                return out_rows
-            return rows_of
-
-        def nbest_lists():
-            self.n_steps = n_host.tolist()
-            out = []
-            for u in range(U):
-                hyps = sorted(ended[u], key=lambda h: h[1], reverse=True)
-                out.append(hyps if nbest is None else hyps[:nbest])
-            return out
-
-        if fused:
-            # One launch searches every utterance to its end (tavsr_ctc_beam_search: records, retiring and end detection on the device);
-            # the host then replays its own per-token processing over the records of the tokens the device searched.
-            key = ("ctc_search", U, T, D, steps, str(dev))
-            cap = self._captured if (self._captured is not None and self._captured["key"] == key) else None
-            if cap is None:
-                cap = self._captured = dict(key=key, graph=None, logp_ctc=ops.empty(U, T, V, like=enc),
-                                            enc_lens=torch.empty(U, dtype=torch.int64, device=dev),
-                                            maxl=torch.empty(U, dtype=torch.int32, device=dev),
-                                            hist=torch.zeros(steps, 3, N, dtype=torch.int32, device=dev),
-                                            n_steps=torch.zeros(U, dtype=torch.int32, device=dev))
-            cap["enc_lens"].copy_(enc_lens)
-            cap["maxl"].copy_(torch.tensor(maxl_h, dtype=torch.int32))
-            ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias), out=cap["logp_ctc"].view(U * T, V))
-            ops.ctc_beam_search(cap["logp_ctc"], cap["enc_lens"], cap["maxl"], cap["hist"], cap["n_steps"], K, self.sos, self.eos,
-                                self.w_ctc, self.w_len, self.maxlenratio == 0.0, D_end)
-            n_dev = cap["n_steps"].cpu()
-            searched = int(n_dev.max())
-            rec = cap["hist"][:searched].cpu().numpy()
-            for i in range(searched):
-                host_step(i, torch.from_numpy(rec[i, 0]).to(torch.int64), torch.from_numpy(rec[i, 2]).view(torch.float32), rows_from_records(i))
-            if bool(active.any()) or not torch.equal(n_host, n_dev):
-                raise RuntimeError(f"tavsr_ctc_beam_search stopped after {n_dev.tolist()} tokens per utterance, the host's end detection "
-                                   f"over its records after {n_host.tolist()} (still searching: {active.tolist()})")
-            return nbest_lists()
-        # A captured step is tied to its buffers, not to a batch: while the shape (utterances, frames, token budget) repeats -
-        # a stream of 4 s clips - the buffers are refilled in place and the hipGraph of the previous call is replayed; capture
-        # and warm-up were 8-10 ms of a 95 ms batch-1 search.
-        key = (U, T, D, steps, str(dev), self.scorers)
-        cap = self._captured if (GRAPH_STEP and self._captured is not None and self._captured["key"] == key) else None
-        if cap is not None:
-            logp_ctc, lens_buf = cap["logp_ctc"], cap["enc_lens"]
-            lens_buf.copy_(enc_lens)
-            enc_lens = lens_buf
-            if has_ctc:
-                ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias), out=logp_ctc.view(U * T, V))
-            if has_dec:
-                self.dec_step.refill(enc)
-            tok, yseq, score, anc, slot_ids, r_prev, s_prev, utt_base = cap["bufs"]
-            full_const = cap["full_const"]
+        if self._ctc_all_tokens and not self.has_lm and CTC_SEARCH_FUSED and ops.ctc_beam_search_ok(self.K, self.V, T):
+            self._search_one_launch(enc, enc_lens, host)
         else:
-            self._captured = None
-            enc_lens = enc_lens.clone()
-            logp_ctc = None
-            if has_ctc:
-                logp_ctc = ops.log_softmax_rows(ops.linear(enc.reshape(U * T, D), ctc.ctc_lo.weight, ctc.ctc_lo.bias)).view(U, T, V)
-            if has_dec:
-                self.dec_step.start(enc, enc_lens, N, K, steps)
-            if self.lm_step is not None:
-                self.lm_step.start(enc, N, steps, K)
-            # running state
-            tok = torch.full((N,), self.sos, dtype=torch.int64, device=dev)
-            yseq = torch.full((N, steps + 2), self.eos, dtype=torch.int64, device=dev)
-            yseq[:, 0] = self.sos
-            score = torch.full((U, K), -float("inf"), device=dev)
-            score[:, 0] = 0.0                                          # one <sos> hypothesis per utterance
-            score = score.view(N)
-            anc = torch.zeros(N, steps, dtype=torch.int32, device=dev)
-            slot_ids = torch.arange(N, dtype=torch.int32, device=dev)
-            r_prev = torch.zeros(N, T, 2, device=dev) if has_ctc else None
-            s_prev = torch.zeros(N, device=dev) if has_ctc else None
-            utt_base = (torch.arange(U, device=dev) * K).view(U, 1)
-            # no decoder and no LM: the full scorers' row is the length bonus alone
-            full_const = torch.full((N, V), self.w_len, device=dev) if not has_dec and self.lm_step is None else None
-        state = dict(r_prev=r_prev, s_prev=s_prev, yseq=yseq, score=score)
+            # A captured step is tied to its buffers, not to a batch: while the shape (utterances, frames, token budget) repeats -
+            # a stream of 4 s clips - the buffers are refilled in place and the hipGraph of the previous call is replayed; capture
+            # and warm-up were 8-10 ms of a 95 ms batch-1 search.
+            key = (U, T, D, host.steps, str(dev), self.scorers)
+            cap = self._captured
+            if GRAPH_STEP and cap is not None and cap.key == key:
+                self._refill(cap, enc, enc_lens, host)
+            else:
+                self._captured = None
+                beam = self._start(enc, enc_lens, host.steps)
+                cap = self._captured = self._capture(key, beam, host) if GRAPH_STEP else None
+            if cap is not None:
+                self._search_replayed(cap, host)
+            else:
+                self._search_eager(beam, host)
+        self.n_steps = host.n_host.tolist()
+        return host.nbest(nbest)
 
-        def device_step(i, dyn):
-            """everything the device does for one token: both scorers, the pre-beam, CTC prefix scores of the candidates,
-            the beam update and the re-ordering of the running state.  ``dyn`` = None: eager launches with the host's
-            step index i.  ``dyn`` = device counters: every buffer is updated IN PLACE and the step index is read from
-            device memory, so the whole step is one captured hipGraph (i is then the pool capacity in steps)."""
-            r_prev, s_prev, yseq, score = state["r_prev"], state["s_prev"], state["yseq"], state["score"]
-            if dyn is None:
-                anc[:, i] = slot_ids + i * N
-                sdyn = None
-            else:
-                # (hypotheses that ended with the previous token - <eos>, or their utterance's last iteration - have left the beam
-                # and column `step` of the ancestor lists is filled: the previous step's re-ordering launch did both, reset_state()
-                # for step 0)
-                sdyn = (dyn["step"],)
-            # full = w_dec * decoder + w_lm * lm + w_len (LengthBonus: 1 per token), summed by the scorers' last launches
-            # the two scorers are independent chains of small launches: the LM runs on the side stream next to the decoder
-            has_lm = self.lm_step is not None
-            spec = dyn is not None and CTC_BESIDE_SCORERS and ops.beam_select_topk_ok(K, V) and C <= V
-            if has_lm:
-                with ops.BranchScope(enabled=SCORERS_PARALLEL) as br:
-                    z_lm = self.lm_step.step(i, tok, anc, sdyn, logits_only=True)
-            # (decoder or CTC scorer absent: the twin below walks the same routes with that scorer's launches and terms left out - a
-            # change to the beam update here belongs there too; this body stays as it is so a hybrid model's launches do not move)
-            if not (has_dec and has_ctc):
-                return device_step_reduced(i, dyn, sdyn, spec, z_lm if has_lm else None, br if has_lm else None)
-            if spec:
-                # on the decoder's queue, in front of its chain: the decoder has ~100 us of slack behind the LM (a third queue for it
-                # made the whole step 45 us SLOWER: profiles/r05_notes.md)
-                r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, dyn["cand_all"], K, i,
-                                                                          step_dev=dyn["step"])
-            full = self.dec_step.step(i, tok, anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len)
-            if has_lm:
-                br.join()
-            if spec:
-                top_s, top_i = ops.beam_select_topk(full, z_lm if has_lm else None, self.w_lm, self.w_len if has_lm else 0.0, psi, psi_abs,
-                                                    eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K, C)
-                ops.beam_reorder(top_i, top_s, dyn["cand_all"], r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, dyn["step"],
-                                 hist=dyn["hist"], maxlen=dyn["maxl"], eos=self.eos)
-                ops.multi_copy_([r_prev, s_prev, yseq, anc, tok, score], list(dyn["shadow"]), inc=dyn["ctr"])
-                return anc, tok
-            if has_lm:
-                ops.log_softmax_rows(z_lm, out=full, alpha=self.w_lm, add=self.w_len, accumulate=True)
-            if PREBEAM_FUSED and C <= 64 and V <= 4096:            # pre-beam on the weighted full scores inside the CTC launch
-                cand, r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step_topk(
-                    logp_ctc, enc_lens, r_prev, s_prev, tok, full, C, K, i, step_dev=None if dyn is None else dyn["step"])
-            else:
-                cand = torch.topk(full, C, dim=-1)[1]
-                r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, cand, K, i,
-                                                                          step_dev=None if dyn is None else dyn["step"])
-            if dyn is not None:
-                # beam update in three launches: weighted scores, top-k, gather of the extended slots' state into the
-                # shadow buffers + one multi-buffer commit (+ the counters); same arithmetic as the torch ops below
-                if ops.beam_combine_topk_ok(K, V):
-                    top_s, top_i = ops.beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K)
-                else:
-                    weighted = ops.beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc)
-                    top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
-                ops.beam_reorder(top_i, top_s, cand, r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, dyn["step"], hist=dyn["hist"],
-                                 maxlen=dyn["maxl"], eos=self.eos)
-                # commit + the step counters (step, step64, stepp1 are views of this one tensor) in one launch
-                ops.multi_copy_([r_prev, s_prev, yseq, anc, tok, score], list(dyn["shadow"]), inc=dyn["ctr"])
-                return anc, tok
+    def _search_one_launch(self, enc, enc_lens, host):
+        """One launch searches every utterance to its end (tavsr_ctc_beam_search: records, retiring and end detection on the device);
+        the host then replays its own per-token processing over the records of the tokens the device searched."""
+        U, T, D = enc.shape
+        key = ("ctc_search", U, T, D, host.steps, str(enc.device))
+        cap = self._captured
+        if cap is None or cap.key != key:
+            cap = self._captured = _Captured(key, None, _OneLaunchBuffers(enc, self.K, self.V, host.steps))
+        b = cap.bufs
+        b.enc_lens.copy_(enc_lens)
+        b.maxl.copy_(torch.tensor(host.maxl, dtype=torch.int32))
+        self._ctc_logp(enc, out=b.logp_ctc)
+        ops.ctc_beam_search(b.logp_ctc, b.enc_lens, b.maxl, b.hist, b.n_steps, self.K, self.sos, self.eos, self.w_ctc, self.w_len,
+                            self.maxlenratio == 0.0, D_END)
+        n_dev = b.n_steps.cpu()
+        rec = b.hist[:int(n_dev.max())].cpu()
+        for i in range(rec.shape[0]):
+            host.step_from_records(rec, i)
+        if bool(host.active.any()) or not torch.equal(host.n_host, n_dev):
+            raise RuntimeError(f"tavsr_ctc_beam_search stopped after {n_dev.tolist()} tokens per utterance, the host's end detection "
+                               f"over its records after {host.n_host.tolist()} (still searching: {host.active.tolist()})")
+
+    def _start(self, enc, enc_lens, steps):
+        """a batch of a new shape: CTC log-probabilities, the scorers' per-search buffers, the beam's running state"""
+        U, T, _ = enc.shape
+        enc_lens = enc_lens.clone()
+        logp_ctc = self._ctc_logp(enc) if self.has_ctc else None
+        if self.has_dec:
+            self.dec_step.start(enc, enc_lens, U * self.K, self.K, steps)
+        if self.has_lm:
+            self.lm_step.start(enc, U * self.K, steps, self.K)
+        return _Beam(self, logp_ctc, enc_lens, T, steps)
+
+    def _refill(self, cap, enc, enc_lens, host):
+        """the next batch of a captured step's shape into the buffers its graph reads"""
+        beam = cap.bufs
+        beam.enc_lens.copy_(enc_lens)
+        if self.has_ctc:
+            self._ctc_logp(enc, out=beam.logp_ctc)
+        if self.has_dec:
+            self.dec_step.refill(enc)
+        beam.reset()
+        cap.dyn.reset()
+        cap.dyn.maxl.copy_(torch.tensor(host.maxl, dtype=torch.int32))
+
+    def _capture(self, key, beam, host):
+        """One token costs ~300 scorer launches plus ~90 small ones for the beam update, all on [N, d]-sized operands.
+        The whole device side of a step is captured once per batch shape - the step index, the positional row, tokens,
+        ancestor lists, CTC state and scores live in fixed device buffers updated in place - and replayed per token;
+        the device also retires ended hypotheses itself and records (token, back-pointer, score) per slot and token, so
+        the host neither uploads anything nor sits on the critical path: it reads the records one token behind the
+        device (end detection, collecting ended hypotheses by back-tracking) while the next step already runs.
+        The step is bound by its chain of dependent small kernels (5-6 us each), not by the host: what shortens it is
+        fewer launches - the K/V append rides in the attention launch, the scorer weights in the log-softmax
+        launches, the beam update is three launches (beam_combine, top-k, beam_reorder) plus one commit."""
+        dyn = _StepCounters(beam, host.maxl, host.steps, self.V)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._device_step(beam, host.steps, dyn)            # warm-up outside the capture; the state is reset below
+            beam.reset()
+            dyn.reset()
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._device_step(beam, host.steps, dyn)
+        return _Captured(key, graph, beam, dyn)
+
+    def _device_step(self, b, i, dyn=None, cand_all=None):
+        """everything the device does for one token: the scorers, the pre-beam, CTC prefix scores of the candidates, the beam update
+        and the re-ordering of the running state ``b``.  ``dyn`` = None: eager launches with the host's step index i (``cand_all``:
+        every token as a candidate list, where ``_ctc_all_tokens``).  ``dyn`` = device counters: every buffer is updated IN PLACE and the
+        step index is read from device memory, so the whole step is one captured hipGraph (i is then the pool capacity in steps;
+        hypotheses that ended with the previous token have left the beam and column `step` of the ancestor lists is filled: the
+        previous step's re-ordering launch did both, ``reset()`` for step 0)."""
+        has_dec, has_ctc, has_lm = self.has_dec, self.has_ctc, self.has_lm
+        if dyn is None:
+            b.anc[:, i] = b.slot_ids + i * b.tok.numel()
+            sd = sdyn = None
+        else:
+            sd, sdyn, cand_all = dyn.step, (dyn.step,), dyn.cand_all
+        # the CTC scores of every token beside the scorers and the beam update behind them in one launch (CTC_BESIDE_SCORERS)
+        spec = dyn is not None and CTC_BESIDE_SCORERS and ops.beam_select_topk_ok(self.K, self.V) and self.C <= self.V
+        z_lm = None
+        if has_lm:                   # the two scorers are independent chains of small launches: the LM runs beside the decoder
+            with ops.BranchScope(enabled=SCORERS_PARALLEL) as br:
+                z_lm = self.lm_step.step(i, b.tok, b.anc, sdyn, logits_only=True)
+        ctc = (None,) * 6
+        if spec and has_ctc:
+            # on the decoder's queue, in front of its chain: the decoder has ~100 us of slack behind the LM (a third queue for it
+            # made the whole step 45 us SLOWER: profiles/r05_notes.md)
+            ctc = self._ctc_prefix(b, i, sd, cand_all)
+        # full = w_dec * decoder + w_lm * lm + w_len (LengthBonus: 1 per token), summed by the scorers' last launches
+        dec = self.dec_step.step(i, b.tok, b.anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len) if has_dec else None
+        if has_lm:
+            br.join()
+        if spec:
+            cand, r_new, psi, psi_abs, eos_s, eos_abs = ctc
+            top = ops.beam_select_topk(dec, z_lm, self.w_lm, self.w_len if (has_lm or not has_dec) else 0.0, psi, psi_abs, eos_s, eos_abs,
+                                       b.s_prev, b.score, self.eos, self.w_ctc, self.K, self.C)
+            return self._commit(b, dyn, top, cand, r_new, psi_abs)
+        full = self._full_row(b, dec, z_lm)
+        if has_ctc:
+            ctc = self._ctc_prefix(b, i, sd, cand_all, full)
+        if dyn is not None:
+            return self._beam_update_captured(b, dyn, full, *ctc)
+        return self._beam_update_eager(b, i, full, *ctc)
+
+    def _full_row(self, b, dec, z_lm):
+        """the full scorers' weighted row [N, V] behind their chains: the LM's log-softmax lands on the decoder's row; no decoder
+        and no LM: the length bonus alone"""
+        if dec is None:
+            return b.full_const if z_lm is None else ops.log_softmax_rows(z_lm, alpha=self.w_lm, add=self.w_len)
+        if z_lm is not None:
+            ops.log_softmax_rows(z_lm, out=dec, alpha=self.w_lm, add=self.w_len, accumulate=True)
+        return dec
+
+    def _ctc_prefix(self, b, i, sd, cand_all, full=None):
+        """CTC prefix scores -> (cand, r_new, psi, psi_abs, eos_s, eos_abs), in one of three forms: of every token (``full`` None: in
+        front of the scorers; or ``_ctc_all_tokens``), of the pre-beam's candidates with the top-k in the launch, or behind torch.topk"""
+        state = (b.logp_ctc, b.enc_lens, b.r_prev, b.s_prev, b.tok)
+        if full is None or self._ctc_all_tokens:
+            return (cand_all,) + tuple(ops.ctc_prefix_step(*state, None if self._ctc_all_tokens else cand_all, self.K, i, step_dev=sd))
+        if PREBEAM_FUSED and self.C <= 64 and self.V <= 4096:            # pre-beam on the weighted full scores inside the CTC launch
+            return ops.ctc_prefix_step_topk(*state, full, self.C, self.K, i, step_dev=sd)
+        cand = torch.topk(full, self.C, dim=-1)[1]
+        return (cand,) + tuple(ops.ctc_prefix_step(*state, cand, self.K, i, step_dev=sd))
+
+    def _beam_update_captured(self, b, dyn, full, cand, r_new, psi, psi_abs, eos_s, eos_abs):
+        """weighted scores and top-k of a captured step (one launch where K * V fits, else two); same arithmetic as the torch ops
+        of ``_beam_update_eager``"""
+        if ops.beam_combine_topk_ok(self.K, self.V):
+            top = ops.beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, b.s_prev, b.score, self.eos, self.w_ctc, self.K)
+        else:
+            weighted = ops.beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, b.s_prev, b.score, self.eos, self.w_ctc)
+            top = torch.topk(weighted.view(b.U, self.K * self.V), self.K, dim=-1)
+        return self._commit(b, dyn, top, cand, r_new, psi_abs)
+
+    def _commit(self, b, dyn, top, cand, r_new, psi_abs):
+        """gather of the extended slots' state into the shadow buffers (+ the records, retiring, the next step's ancestor column), then
+        one multi-buffer commit that also counts the step"""
+        top_s, top_i = top
+        ops.beam_reorder(top_i, top_s, cand, r_new, psi_abs, b.yseq, b.anc, dyn.shadow, self.K, self.V, dyn.step, hist=dyn.hist,
+                         maxlen=dyn.maxl, eos=self.eos)
+        ops.multi_copy_(b.live(), [t for t in dyn.shadow if t is not None], inc=dyn.ctr)
+
+    def _beam_update_eager(self, b, i, full, cand, r_new, psi, psi_abs, eos_s, eos_abs):
+        """the beam update in torch ops; the running state is rebound to the gathered tensors"""
+        N, V, score = b.tok.numel(), self.V, b.score
+        if self.has_ctc:
             is_eos_c = cand == self.eos
             psi = torch.where(is_eos_c, eos_s.unsqueeze(1), psi)
             psi_abs = torch.where(is_eos_c, eos_abs.unsqueeze(1), psi_abs)
-            ctc_full = torch.full((N, V), LOGZERO, device=dev) - s_prev.unsqueeze(1)
+            ctc_full = torch.full((N, V), LOGZERO, device=score.device) - b.s_prev.unsqueeze(1)
             ctc_full[:, self.eos] = eos_s
             ctc_full.scatter_(1, cand, psi)
             weighted = full + self.w_ctc * ctc_full + score.unsqueeze(1)
-            top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
-            prev = (top_i // V + utt_base).view(N)                  # slot the new hypothesis extends
-            new_tok = (top_i % V).view(N)
-            # CTC state of the chosen candidate
-            cidx = (cand[prev] == new_tok.unsqueeze(1)).float().argmax(dim=1)
-            state["r_prev"], state["s_prev"] = r_new[prev, :, :, cidx], psi_abs[prev, cidx]
-            yseq = yseq[prev]
-            yseq[:, i + 1] = new_tok
-            state["yseq"], state["score"] = yseq, top_s.view(N)
-            return anc[prev], new_tok
-
-        def device_step_reduced(i, dyn, sdyn, spec, z_lm, br):
-            """the step with the decoder or the CTC scorer absent (espnet drops a scorer that is None or has weight 0): the same
-            routes as above - one-launch beam update, beam_combine_topk, torch ops - with the absent scorer's launches and terms left
-            out (null operands of the beam kernels, include/tavsr.h)"""
-            r_prev, s_prev, yseq, score = state["r_prev"], state["s_prev"], state["yseq"], state["score"]
-            has_lm = z_lm is not None
-            sd = None if dyn is None else dyn["step"]
-            live = [t for t in (r_prev, s_prev) if t is not None] + [yseq, anc, tok, score]
-            shadow = None if dyn is None else [t for t in dyn["shadow"] if t is not None]
-            if spec:
-                psi = psi_abs = eos_s = eos_abs = r_new = None
-                if has_ctc:
-                    # (without pre-beam: the form that scores every token with the one-launch search's sums, bit for bit)
-                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok,
-                                                                              dyn["cand_all"] if self.pre_beam else None, K, i, step_dev=sd)
-                dec = self.dec_step.step(i, tok, anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len) if has_dec else None
-                if has_lm:
-                    br.join()
-                top_s, top_i = ops.beam_select_topk(dec, z_lm, self.w_lm, self.w_len if (has_lm or not has_dec) else 0.0, psi, psi_abs,
-                                                    eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K, C)
-                ops.beam_reorder(top_i, top_s, dyn["cand_all"], r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, sd, hist=dyn["hist"],
-                                 maxlen=dyn["maxl"], eos=self.eos)
-                ops.multi_copy_(live, shadow, inc=dyn["ctr"])
-                return anc, tok
-            if has_dec:
-                full = self.dec_step.step(i, tok, anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len)
-                if has_lm:
-                    br.join()
-                    ops.log_softmax_rows(z_lm, out=full, alpha=self.w_lm, add=self.w_len, accumulate=True)
-            elif has_lm:
-                br.join()
-                full = ops.log_softmax_rows(z_lm, alpha=self.w_lm, add=self.w_len)
-            else:
-                full = full_const
-            cand = r_new = psi = psi_abs = eos_s = eos_abs = None
-            if has_ctc:
-                if not self.pre_beam:                                  # every token is scored (ctc_weight 1, or fewer tokens than 1.5 beam)
-                    cand = dyn["cand_all"] if dyn is not None else cand_eager
-                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, None, K, i, step_dev=sd)
-                elif PREBEAM_FUSED and C <= 64 and V <= 4096:
-                    cand, r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step_topk(logp_ctc, enc_lens, r_prev, s_prev, tok, full, C, K,
-                                                                                         i, step_dev=sd)
-                else:
-                    cand = torch.topk(full, C, dim=-1)[1]
-                    r_new, psi, psi_abs, eos_s, eos_abs = ops.ctc_prefix_step(logp_ctc, enc_lens, r_prev, s_prev, tok, cand, K, i, step_dev=sd)
-            if dyn is not None:
-                if ops.beam_combine_topk_ok(K, V):
-                    top_s, top_i = ops.beam_combine_topk(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc, K)
-                else:
-                    weighted = ops.beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, self.eos, self.w_ctc)
-                    top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
-                ops.beam_reorder(top_i, top_s, cand, r_new, psi_abs, yseq, anc, dyn["shadow"], K, V, sd, hist=dyn["hist"],
-                                 maxlen=dyn["maxl"], eos=self.eos)
-                ops.multi_copy_(live, shadow, inc=dyn["ctr"])
-                return anc, tok
-            if has_ctc:
-                is_eos_c = cand == self.eos
-                psi = torch.where(is_eos_c, eos_s.unsqueeze(1), psi)
-                psi_abs = torch.where(is_eos_c, eos_abs.unsqueeze(1), psi_abs)
-                ctc_full = torch.full((N, V), LOGZERO, device=dev) - s_prev.unsqueeze(1)
-                ctc_full[:, self.eos] = eos_s
-                ctc_full.scatter_(1, cand, psi)
-                weighted = full + self.w_ctc * ctc_full + score.unsqueeze(1)
-            else:
-                weighted = full + score.unsqueeze(1)
-            top_s, top_i = torch.topk(weighted.view(U, K * V), K, dim=-1)
-            prev = (top_i // V + utt_base).view(N)                  # slot the new hypothesis extends
-            new_tok = (top_i % V).view(N)
-            if has_ctc:                                             # CTC state of the chosen candidate
-                cidx = (cand[prev] == new_tok.unsqueeze(1)).float().argmax(dim=1)
-                state["r_prev"], state["s_prev"] = r_new[prev, :, :, cidx], psi_abs[prev, cidx]
-            yseq = yseq[prev]
-            yseq[:, i + 1] = new_tok
-            state["yseq"], state["score"] = yseq, top_s.view(N)
-            return anc[prev], new_tok
-
-        cand_eager = None
-        if has_ctc and not self.pre_beam and not (has_dec and has_ctc):
-            cand_eager = torch.arange(V, dtype=torch.int64, device=dev).repeat(N, 1)
-
-        def reset_state():
-            tok.fill_(self.sos)
-            yseq.fill_(self.eos)
-            yseq[:, 0] = self.sos
-            score.fill_(NEG_INF)
-            score.view(U, K)[:, 0] = 0.0
-            anc.zero_()
-            anc[:, 0] = slot_ids                                      # step 0's own key / value rows
-            if has_ctc:
-                r_prev.zero_()
-                s_prev.zero_()
-
-        graph = dyn = None
-        if cap is not None:
-            graph, dyn = cap["graph"], cap["dyn"]
-            reset_state()
-            dyn["ctr"].copy_(torch.tensor([0, 1], dtype=torch.int64))
-            dyn["maxl"].copy_(torch.tensor(maxl_h, dtype=torch.int32))
-        elif GRAPH_STEP:
-            # One token costs ~300 scorer launches plus ~90 small ones for the beam update, all on [N, d]-sized operands.
-            # The whole device side of a step is captured once per decode() - the step index, the positional row, tokens,
-            # ancestor lists, CTC state and scores live in fixed device buffers updated in place - and replayed per token;
-            # the device also retires ended hypotheses itself and records (token, back-pointer, score) per slot and token, so
-            # the host neither uploads anything nor sits on the critical path: it reads the records one token behind the
-            # device (end detection, collecting ended hypotheses by back-tracking) while the next step already runs.
-            # The step is bound by its chain of dependent small kernels (5-6 us each), not by the host: what shortens it is
-            # fewer launches - the K/V append rides in the attention launch, the scorer weights in the log-softmax
-            # launches, the beam update is three launches (beam_combine, top-k, beam_reorder) plus one commit.
-            ctr = torch.tensor([0, 1], dtype=torch.int64, device=dev)          # (i, i + 1); the kernels read i as int32
-            dyn = dict(ctr=ctr, step64=ctr[0:1], stepp1=ctr[1:2], step=ctr.view(torch.int32)[0:1],     # (low word: little endian)
-                       maxl=torch.tensor(maxl_h, dtype=torch.int32, device=dev),
-                       hist=torch.zeros(steps, 3, N, dtype=torch.int32, device=dev),
-                       cand_all=torch.arange(V, dtype=torch.int64, device=dev).repeat(N, 1),      # every token a "candidate" of the CTC scorer
-                       shadow=(torch.empty_like(r_prev) if has_ctc else None, torch.empty_like(s_prev) if has_ctc else None,
-                               torch.empty_like(yseq), torch.empty_like(anc), torch.empty_like(tok), torch.empty_like(score)))
-            if not has_ctc:
-                dyn["cand_all"] = None
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                device_step(steps, dyn)                             # warm-up outside the capture; the state is reset below
-                reset_state()
-                ctr.copy_(torch.tensor([0, 1], dtype=torch.int64))
-            torch.cuda.current_stream().wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                device_step(steps, dyn)
-            self._captured = dict(key=key, graph=graph, dyn=dyn, logp_ctc=logp_ctc, enc_lens=enc_lens,
-                                  bufs=(tok, yseq, score, anc, slot_ids, r_prev, s_prev, utt_base), full_const=full_const)
-        if graph is not None:
-            hist = dyn["hist"]
-            need = steps * 3 * N                                    # page-locked landing zone of the records: ONE buffer that
-            if self._pinned is None or self._pinned.numel() < need:   # grows to the largest search seen
-                self._pinned = torch.empty(max(need, 1 << 16), dtype=torch.int32, pin_memory=True)
-            pin = self._pinned[:need].view(steps, 3, N)
-            rec = pin.numpy()                                       # same memory: rec[token][0 / 1 / 2][slot]
-
-            events, done = [], 0
-            timing = os.environ.get("TAVSR_DECODE_TIMING") == "1"   # host-side cost of a token: replay call / record processing
-            t_replay = t_host = t_wait = 0.0
-            import time as _time
-            # the record of token i leaves behind step i on the search queue itself (see RECORD_QUEUE for the queue of their own the
-            # records had, and what the event it needs costs the next replay)
-            main_q = torch.cuda.current_stream()
-            if self._copy_q is None:
-                self._copy_q = torch.cuda.Stream() if RECORD_QUEUE else main_q
-            copy_q = self._copy_q
-            copy_q.wait_stream(main_q)
-            for i in range(steps):
-                t0 = _time.perf_counter()
-                graph.replay()
-                if copy_q is not main_q:
-                    stepped = torch.cuda.Event()
-                    stepped.record(main_q)
-                    copy_q.wait_event(stepped)
-                with torch.cuda.stream(copy_q):
-                    pin[i].copy_(hist[i], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_q)
-                events.append(ev)
-                t1 = _time.perf_counter()
-                while done < i and bool(active.any()):              # the host works one token behind the device
-                    events[done].synchronize()
-                    t2 = _time.perf_counter()
-                    host_step(done, pin[done, 0].to(torch.int64), pin[done, 2].view(torch.float32), rows_from_records(done))
-                    done += 1
-                    t_wait += t2 - t1
-                    t_host += _time.perf_counter() - t2
-                t_replay += t1 - t0
-                if not bool(active.any()):
-                    break
-            if timing:
-                n_ = max(1, len(events))
-                print(f"decode timing (host, per token, N = {N}): replay + copy + event {1e6 * t_replay / n_:.0f} us, waiting for the "
-                      f"device {1e6 * t_wait / n_:.0f} us, record processing {1e6 * t_host / n_:.0f} us", flush=True)
-            while done < len(events) and bool(active.any()):
-                events[done].synchronize()
-                host_step(done, pin[done, 0].to(torch.int64), pin[done, 2].view(torch.float32), rows_from_records(done))
-                done += 1
-            main_q.wait_stream(copy_q)
-            main_q.synchronize()                                    # a step the device ran ahead may still be in flight
         else:
-            for i in range(steps):
-                anc, tok = device_step(i, None)
-                yseq, score = state["yseq"], state["score"]
-                kill = host_step(i, tok.cpu(), score.cpu(), lambda idx: yseq[idx.to(dev)].cpu().tolist())
-                if bool(kill.any()):
-                    state["score"] = torch.where(kill.to(dev), torch.full_like(score, NEG_INF), score)
-                if not bool(active.any()):
-                    break
-        return nbest_lists()
+            weighted = full + score.unsqueeze(1)
+        top_s, top_i = torch.topk(weighted.view(b.U, self.K * V), self.K, dim=-1)
+        prev = (top_i // V + b.utt_base).view(N)                # slot the new hypothesis extends
+        new_tok = (top_i % V).view(N)
+        if self.has_ctc:                                        # CTC state of the chosen candidate
+            cidx = (cand[prev] == new_tok.unsqueeze(1)).float().argmax(dim=1)
+            b.r_prev, b.s_prev = r_new[prev, :, :, cidx], psi_abs[prev, cidx]
+        yseq = b.yseq[prev]
+        yseq[:, i + 1] = new_tok
+        b.yseq, b.score, b.anc, b.tok = yseq, top_s.view(N), b.anc[prev], new_tok
+
+    def _search_eager(self, b, host):
+        """token by token with the host in the loop: eager launches, the host's step index"""
+        dev, N = b.tok.device, b.tok.numel()
+        cand_all = torch.arange(self.V, dtype=torch.int64, device=dev).repeat(N, 1) if self._ctc_all_tokens else None
+        for i in range(host.steps):
+            self._device_step(b, i, None, cand_all)
+            yseq, score = b.yseq, b.score
+            kill = host.step(i, b.tok.cpu(), score.cpu(), lambda idx: yseq[idx.to(dev)].cpu().tolist())
+            if bool(kill.any()):
+                b.score = torch.where(kill.to(dev), torch.full_like(score, -float("inf")), score)
+            if not bool(host.active.any()):
+                break
+
+    def _search_replayed(self, cap, host):
+        """one graph replay per token; the host processes the records one token behind the device"""
+        graph, hist = cap.graph, cap.dyn.hist
+        steps, _, N = hist.shape
+        need = steps * 3 * N                                    # page-locked landing zone of the records: ONE buffer that
+        if self._pinned is None or self._pinned.numel() < need:   # grows to the largest search seen
+            self._pinned = torch.empty(max(need, 1 << 16), dtype=torch.int32, pin_memory=True)
+        pin = self._pinned[:need].view(steps, 3, N)             # pin[token][0 / 1 / 2][slot]
+        events, done = [], 0
+        timing = os.environ.get("TAVSR_DECODE_TIMING") == "1"   # host-side cost of a token: replay call / record processing
+        t_replay = t_host = t_wait = 0.0
+        # the record of token i leaves behind step i on the search queue itself (see RECORD_QUEUE for the queue of their own the
+        # records had, and what the event it needs costs the next replay)
+        main_q = torch.cuda.current_stream()
+        if self._copy_q is None:
+            self._copy_q = torch.cuda.Stream() if RECORD_QUEUE else main_q
+        copy_q = self._copy_q
+        copy_q.wait_stream(main_q)
+        for i in range(steps):
+            t0 = time.perf_counter()
+            graph.replay()
+            if copy_q is not main_q:
+                stepped = torch.cuda.Event()
+                stepped.record(main_q)
+                copy_q.wait_event(stepped)
+            with torch.cuda.stream(copy_q):
+                pin[i].copy_(hist[i], non_blocking=True)
+                ev = torch.cuda.Event()
+                ev.record(copy_q)
+            events.append(ev)
+            t1 = time.perf_counter()
+            while done < i and bool(host.active.any()):         # the host works one token behind the device
+                events[done].synchronize()
+                t2 = time.perf_counter()
+                host.step_from_records(pin, done)
+                done += 1
+                t_wait += t2 - t1
+                t_host += time.perf_counter() - t2
+            t_replay += t1 - t0
+            if not bool(host.active.any()):
+                break
+        if timing:
+            n_ = max(1, len(events))
+            print(f"decode timing (host, per token, N = {N}): replay + copy + event {1e6 * t_replay / n_:.0f} us, waiting for the "
+                  f"device {1e6 * t_wait / n_:.0f} us, record processing {1e6 * t_host / n_:.0f} us", flush=True)
+        while done < len(events) and bool(host.active.any()):
+            events[done].synchronize()
+            host.step_from_records(pin, done)
+            done += 1
+        main_q.wait_stream(copy_q)
+        main_q.synchronize()                                    # a step the device ran ahead may still be in flight
+
+
+class _Beam:
+    """the running state of a token-by-token search in device buffers: a captured step updates them in place (and ``reset()`` starts
+    the next search in them), the eager route rebinds them step by step"""
+
+    def __init__(self, search, logp_ctc, enc_lens, T, steps):
+        K, V, dev = search.K, search.V, enc_lens.device
+        U = enc_lens.numel()
+        N = U * K
+        self.U, self.K, self.sos, self.eos = U, K, search.sos, search.eos
+        self.logp_ctc, self.enc_lens = logp_ctc, enc_lens
+        self.tok = torch.full((N,), self.sos, dtype=torch.int64, device=dev)
+        self.yseq = torch.full((N, steps + 2), self.eos, dtype=torch.int64, device=dev)
+        self.yseq[:, 0] = self.sos
+        score = torch.full((U, K), -float("inf"), device=dev)
+        score[:, 0] = 0.0                                          # one <sos> hypothesis per utterance
+        self.score = score.view(N)
+        self.anc = torch.zeros(N, steps, dtype=torch.int32, device=dev)       # per hypothesis the key / value rows of its history
+        self.slot_ids = torch.arange(N, dtype=torch.int32, device=dev)
+        self.r_prev = torch.zeros(N, T, 2, device=dev) if search.has_ctc else None
+        self.s_prev = torch.zeros(N, device=dev) if search.has_ctc else None
+        self.utt_base = (torch.arange(U, device=dev) * K).view(U, 1)
+        # no decoder and no LM: the full scorers' row is the length bonus alone
+        self.full_const = torch.full((N, V), search.w_len, device=dev) if not search.has_dec and not search.has_lm else None
+
+    def live(self):
+        """the buffers a step's commit overwrites, in the order of ``_StepCounters.shadow``"""
+        return [t for t in (self.r_prev, self.s_prev) if t is not None] + [self.yseq, self.anc, self.tok, self.score]
+
+    def reset(self):
+        self.tok.fill_(self.sos)
+        self.yseq.fill_(self.eos)
+        self.yseq[:, 0] = self.sos
+        self.score.fill_(-float("inf"))
+        self.score.view(self.U, self.K)[:, 0] = 0.0
+        self.anc.zero_()
+        self.anc[:, 0] = self.slot_ids                            # step 0's own key / value rows
+        if self.r_prev is not None:
+            self.r_prev.zero_()
+            self.s_prev.zero_()
+
+
+class _StepCounters:
+    """what a captured step reads and writes beside the beam: the device-side step counter, the token budgets, the per-token records
+    (token, back-pointer, score bits), every token as a candidate list of the CTC scorer, the shadow buffers of the beam update"""
+
+    def __init__(self, beam, maxl, steps, V):
+        dev, N = beam.tok.device, beam.tok.numel()
+        self.ctr = torch.tensor([0, 1], dtype=torch.int64, device=dev)          # (i, i + 1), counted by the commit launch
+        self.step = self.ctr.view(torch.int32)[0:1]                             # the kernels read i as int32 (low word: little endian)
+        self.maxl = torch.tensor(maxl, dtype=torch.int32, device=dev)
+        self.hist = torch.zeros(steps, 3, N, dtype=torch.int32, device=dev)
+        self.cand_all = torch.arange(V, dtype=torch.int64, device=dev).repeat(N, 1) if beam.r_prev is not None else None
+        self.shadow = tuple(None if t is None else torch.empty_like(t)
+                            for t in (beam.r_prev, beam.s_prev, beam.yseq, beam.anc, beam.tok, beam.score))
+
+    def reset(self):
+        self.ctr.copy_(torch.tensor([0, 1], dtype=torch.int64))
+
+
+class _OneLaunchBuffers:
+    """operands and results of the one-launch CTC search (tavsr_ctc_beam_search), re-used while the shape repeats"""
+
+    def __init__(self, enc, K, V, steps):
+        U, T, _ = enc.shape
+        dev = enc.device
+        self.logp_ctc = ops.empty(U, T, V, like=enc)
+        self.enc_lens = torch.empty(U, dtype=torch.int64, device=dev)
+        self.maxl = torch.empty(U, dtype=torch.int32, device=dev)
+        self.hist = torch.zeros(steps, 3, U * K, dtype=torch.int32, device=dev)
+        self.n_steps = torch.zeros(U, dtype=torch.int32, device=dev)
+
+
+class _Captured:
+    """what a decode() keeps for the next batch of the same shape: the captured step (``graph``; None on the one-launch route), the
+    buffers it reads and writes (``bufs``: ``_Beam`` / ``_OneLaunchBuffers``) and its device counters (``dyn``)"""
+
+    def __init__(self, key, graph, bufs, dyn=None):
+        self.key, self.graph, self.bufs, self.dyn = key, graph, bufs, dyn
+
+    def __getitem__(self, name):
+        """the keyed view of the same objects that earlier callers read: ``["graph"]``, ``["logp_ctc"]``, ``["bufs"][5]`` (r_prev)"""
+        if name == "bufs":
+            b = self.bufs
+            return (b.tok, b.yseq, b.score, b.anc, b.slot_ids, b.r_prev, b.s_prev, b.utt_base)
+        for o in (self, self.bufs, self.dyn):
+            if hasattr(o, name):
+                return getattr(o, name)
+        raise KeyError(name)
 
 
 class CapturedEncode:

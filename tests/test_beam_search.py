@@ -155,7 +155,7 @@ def test_captured_step_is_reused_for_the_next_batch_of_the_same_shape():
         graphs = []
         for enc, olens in batches:
             got = search.decode(enc, olens)
-            graphs.append(search._captured["graph"])
+            graphs.append(search._captured.graph)
             want = BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5).decode(enc, olens)
             for u in range(2):
                 assert [h[0] for h in got[u]] == [h[0] for h in want[u]], u
@@ -185,15 +185,49 @@ def test_reused_captured_step_follows_a_change_of_the_weights():
         enc, olens = pm.encode(x, torch.tensor([160, 120]).cuda())
         search = BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5)
         before = search.decode(enc, olens)
-        graph = search._captured["graph"]
+        graph = search._captured.graph
         other = TransformerLM(len(TOKENS_EN), **LM_KW)
         fill_parameters_(other, seed=66)
         plm.load_state_dict(other.state_dict())                      # copy_ in place: same storages, new versions
         for l in pm.decoder.decoders:
             l.self_attn.linear_q.weight.mul_(0.5)
         got = search.decode(enc, olens)
-        assert search._captured["graph"] is graph
+        assert search._captured.graph is graph
         want = BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5).decode(enc, olens)
+    assert [h[0] for h in got[0]] != [h[0] for h in before[0]] or [h[1] for h in got[0]] != [h[1] for h in before[0]]
+    for u in range(2):
+        assert [h[0] for h in got[u]] == [h[0] for h in want[u]], u
+        assert [h[1] for h in got[u]] == [h[1] for h in want[u]], u
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("graph_step", [True, False])
+def test_first_decode_follows_a_change_of_the_weights_since_construction(monkeypatch, graph_step):
+    """the parameters change in place AFTER the search object was built and BEFORE its first decode (load_state_dict
+    after construction, optimizer steps before the first validation decode).  The derived copies were made at construction: the first
+    decode must re-derive them, i.e. give what a search object built after the change gives - and not what the old weights give."""
+    from tavsr.inference import beam_search as PBS
+    from tavsr.lm.transformer_lm import TransformerLM
+    from tavsr.tasks.asr import ASRTask
+    monkeypatch.setattr(PBS, "GRAPH_STEP", graph_step)
+    conf = asr_conf(num_blocks=2, dec_blocks=2)
+    conf["token_list"] = TOKENS_EN
+    pm = ASRTask.build_model(argparse.Namespace(**conf)).eval()
+    fill_parameters_(pm, seed=5)
+    plm = TransformerLM(len(TOKENS_EN), **LM_KW).eval()
+    fill_parameters_(plm, seed=6)
+    pm, plm = pm.cuda(), plm.cuda()
+    with torch.no_grad():
+        x = synth((2, 160, 80), seed=7).cuda()
+        enc, olens = pm.encode(x, torch.tensor([160, 120]).cuda())
+        before = PBS.BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5).decode(enc, olens)
+        search = PBS.BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5)
+        for l in pm.decoder.decoders:
+            l.self_attn.linear_q.weight.mul_(0.5)
+        plm.encoder.encoders[0].self_attn.linear_q.weight.mul_(0.5)
+        got = search.decode(enc, olens)
+        assert (search._captured is not None) == graph_step
+        want = PBS.BatchBeamSearch(pm, plm, 10, 0.1, 0.6, 0.5).decode(enc, olens)
     assert [h[0] for h in got[0]] != [h[0] for h in before[0]] or [h[1] for h in got[0]] != [h[1] for h in before[0]]
     for u in range(2):
         assert [h[0] for h in got[u]] == [h[0] for h in want[u]], u

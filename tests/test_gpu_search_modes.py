@@ -96,7 +96,7 @@ def test_ctc_only_search_matches_oracle(monkeypatch, beam, pen, fused):
     _, _, enc, olens = _oracle()
     search = PBS.BatchBeamSearch(_product(1.0), None, beam, 1.0, 0.0, pen)
     hip = search.decode(enc.cuda(), olens.cuda())
-    assert (search._captured["graph"] is None) == fused          # the route taken: one launch / a captured step
+    assert (search._captured.graph is None) == fused          # the route taken: one launch / a captured step
     _check_against_reference(hip, _reference(False, True, beam, 0.0, pen))
 
 
@@ -116,8 +116,29 @@ def test_attention_only_search_matches_oracle(beam, lm_w):
     _, _, enc, olens = _oracle()
     search = BatchBeamSearch(_product(0.0), _product_lm() if lm_w else None, beam, 0.0, lm_w, 0.5)
     hip = search.decode(enc.cuda(), olens.cuda())
-    assert search._captured["logp_ctc"] is None and search._captured["bufs"][5] is None       # no CTC buffers
+    assert search._captured.bufs.logp_ctc is None and search._captured.bufs.r_prev is None       # no CTC buffers
     _check_against_reference(hip, _reference(True, False, beam, lm_w, 0.5))
+
+
+@pytest.mark.parametrize("beside", [True, False])
+@pytest.mark.parametrize("lm_w", [0.0, 0.6])
+def test_hybrid_model_without_pre_beam_matches_oracle(monkeypatch, lm_w, beside):
+    """a hybrid model at ctc_weight 1.0 WITHOUT skip_zero_weight: the decoder still runs (at weight 0) and there is no pre-beam, so the
+    CTC launch is handed every token as a candidate list - the form ``BatchBeamSearch._ctc_all_tokens`` keeps apart from the reduced
+    step's ``cand=None``; beam 5: the one-launch beam update behind the scorers (CTC_BESIDE_SCORERS), and the launches behind them.
+    espnet drops the decoder at weight 0: the oracle's search is the CTC (+ LM) one.  Smallest gap between the oracle's first and
+    second hypothesis: 1.44e-3 absolute without LM (utterance 0, score -82.35; 4.1e-3 and 2.6e-2 for the others), 0.126 with the LM -
+    the first about ten times the fp32 error of such a score, so the best hypothesis is compared token for token."""
+    from tavsr import ops
+    from tavsr.inference import beam_search as PBS
+    monkeypatch.setattr(PBS, "CTC_BESIDE_SCORERS", beside)
+    _, _, enc, olens = _oracle()
+    search = PBS.BatchBeamSearch(_product(), _product_lm() if lm_w else None, 5, 1.0, lm_w, 0.5, skip_zero_weight=False)
+    assert search.has_dec and search.has_ctc and not search.pre_beam and search.C == V and not search._ctc_all_tokens
+    assert ops.beam_select_topk_ok(5, V)
+    hip = search.decode(enc.cuda(), olens.cuda())
+    assert search._captured.graph is not None
+    _check_against_reference(hip, _reference(False, True, 5, lm_w, 0.5))
 
 
 @pytest.mark.parametrize("fused", [True, False])
@@ -156,7 +177,7 @@ def test_one_launch_search_equals_the_stepwise_route(monkeypatch, U, T, K, scale
         search = PBS.BatchBeamSearch(_product(1.0), None, K, 1.0, 0.0, 0.5)
         outs.append(search.decode(enc, lens))
         steps.append(search.n_steps)
-        assert (search._captured["graph"] is None) == fused
+        assert (search._captured.graph is None) == fused
     print(f"U {U} T {T} K {K}: tokens searched {steps[0]}, hypotheses {[len(o) for o in outs[0]]}")
     assert steps[0] == steps[1] and all(1 <= n <= int(l) for n, l in zip(steps[0], lens))
     assert all(len(o) > 0 for o in outs[0])
@@ -176,7 +197,7 @@ def test_one_launch_search_with_a_large_lattice_equals_the_stepwise_route(monkey
         monkeypatch.setattr(PBS, "CTC_SEARCH_FUSED", fused)
         search = PBS.BatchBeamSearch(_product(1.0), None, K, 1.0, 0.0, 0.5, maxlenratio=-12)
         outs.append(search.decode(enc, lens))
-        assert (search._captured["graph"] is None) == fused and search.n_steps == [12] * U
+        assert (search._captured.graph is None) == fused and search.n_steps == [12] * U
     assert all(len(o) == K for o in outs[0]) and outs[0] == outs[1]
 
 
@@ -193,7 +214,7 @@ def test_a_shape_the_one_launch_search_refuses_takes_the_stepwise_route(monkeypa
         monkeypatch.setattr(PBS, "CTC_SEARCH_FUSED", fused)
         search = PBS.BatchBeamSearch(_product(1.0), None, K, 1.0, 0.0, 0.5, maxlenratio=-12)
         outs.append(search.decode(enc, lens))
-        assert search._captured["graph"] is not None and search.n_steps == [12]
+        assert search._captured.graph is not None and search.n_steps == [12]
     assert len(outs[0][0]) > 0 and outs[0] == outs[1]
 
 
