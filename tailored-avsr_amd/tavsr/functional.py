@@ -14,14 +14,12 @@ from __future__ import annotations
 
 import math
 import os
-from typing import List, Optional
+from typing import Any, List, NamedTuple, Optional
 
 import torch
 
 from . import ops
 from ._lib import guarded
-
-EPS_ESPNET = 1e-12  # espnet LayerNorm eps
 
 # Does the node being run have a backward pass?  Set by every Function.forward from ctx.needs_input_grad: a forward under
 # no_grad / in eval mode does not write the [M, 2048] pre-activations of its feed-forward and cgMLP blocks (26 MB each).
@@ -48,235 +46,56 @@ def _note_ctx(ctx):
 
 
 # ------------------------------------------------------------------------------------------------
-# building blocks shared by the Functions (plain python, explicit saved state)
+# building blocks shared by the Functions: tavsr/layer_blocks.py (re-exported: tests and scripts reach them as F_._FFN, ...)
 # ------------------------------------------------------------------------------------------------
-def _drop_(x, p):
-    """in-place train-mode dropout; returns the token that regenerates the mask (None when p == 0)."""
-    if not p or p <= 0.0:
-        return None
-    return ops.dropout(x, p, out=x)[1]
+from .layer_blocks import (EPS_ESPNET, FF_PARAMS, FFM_PARAMS, AttnBranch, AttnSaved, CgmlpBranch, CgmlpSaved, FFNSaved,  # noqa: E402,F401
+                           _AttnFused, _drop_, _drop_bwd, _drop_bwd_, _FFN, _SelfAttnCore)
 
-
-def _drop_bwd_(dy, tok):
-    """in-place backward of _drop_ (same mask, same scale); no-op without a token."""
-    if tok is not None:
-        ops.dropout(dy, tok[0], out=dy, token=tok)
-    return dy
-
-
-def _drop_bwd(dy, tok):
-    """out-of-place variant for gradients that are still needed unmasked (residual paths)."""
-    return dy if tok is None else ops.dropout(dy, tok[0], token=tok)[0]
-
-
-class _FFN:
-    """y = x + scale * drop(W2 drop(act(W1 LN(x) + b1)) + b2)   (encoder_layer.py:192-194,312-314; decoder FFN;
-    the inner dropout is PositionwiseFeedForward's, the outer one the layer's: both rate ``p`` in the reference)."""
-
-    @staticmethod
-    def fwd(x, ln_w, ln_b, w1, b1, w2, b2, act, scale, eps=EPS_ESPNET, p=0.0, save=True):
-        """``save``: keep what the backward needs (the [M, hidden] pre-activations); False for passes without one."""
-        if ops.ffn2_usable(x, w1, act):      # streaming chain kernel (csrc/ffn2.hip) + finishing launch; GEMM-path masks
-            y, (n, mean, rstd, z, h, t_in, t_out), _, _ = ops.ffn2_fwd(x, ln_w, ln_b, eps, w1, b1, w2, b2, act, scale, p=p,
-                                                                       save=save)
-            return y, (x, mean, rstd, n, z, h, t_in, t_out)
-        n, mean, rstd = ops.layernorm_fwd(x, ln_w, ln_b, eps)
-        if save:
-            h, z, t_in = ops.linear_drop(n, w1, b1, p, act=act, save_z=True)     # both dropouts ride in the GEMM epilogues
-        else:
-            (h, t_in), z = ops.linear_drop(n, w1, b1, p, act=act), None
-        y, t_out = ops.linear_drop(h, w2, b2, p, alpha=scale, res=x)             # x + scale * dropout(.)
-        return y, (x, mean, rstd, n, z, h, t_in, t_out)
-
-    @staticmethod
-    def fwd_ln(x, ln_w, ln_b, w1, b1, w2, b2, act, scale, norms, eps=EPS_ESPNET, p=0.0, save=True):
-        """``fwd`` plus the LayerNorms (espnet eps) the consumers of y start with: ``norms`` = [(gamma, beta), ...] (at most
-        two) -> (y, saved, [n_k], mean, rstd).  On the streaming path they ride in the finishing launch (one statistics
-        pass for all of them); otherwise they are the usual LayerNorm launches."""
-        if ops.ffn2_usable(x, w1, act):
-            y, (n, mean, rstd, z, h, t_in, t_out), outs, (m2, r2) = ops.ffn2_fwd(
-                x, ln_w, ln_b, eps, w1, b1, w2, b2, act, scale, p=p, save=save, ln2=norms, ln2_eps=EPS_ESPNET, ln2_stats=save)
-            return y, (x, mean, rstd, n, z, h, t_in, t_out), outs, m2, r2
-        y, saved = _FFN.fwd(x, ln_w, ln_b, w1, b1, w2, b2, act, scale, eps=eps, p=p, save=save)
-        outs, m2, r2 = [], None, None
-        for g, b in norms:
-            o, m2, r2 = ops.layernorm_fwd(y, g, b, EPS_ESPNET)
-            outs.append(o)
-        return y, saved, outs, m2, r2
-
-    @staticmethod
-    def bwd(dy, saved, ln_w, w1, w2, act, scale, grp=None, lng=None, chain=True, dyd=None, out_drop=None):
-        """returns dx (includes the residual path) and grads (ln_w, ln_b, w1, b1, w2, b2).  ``grp`` (ops.WgradGroup)
-        defers the two weight gradients to the caller's grouped launch.  ``chain``: the two activation gradients as one
-        streaming launch (ops.ffn2_bwd_dx) instead of two dgrad GEMMs - callers that run two of these blocks side by side
-        on two launch queues pass False (a chain kernel owns every CU; two of them serialise, two GEMM sequences overlap)."""
-        x, mean, rstd, n, z, h, t_in, t_out = saved
-        wgrad = ops.linear_dw if grp is None else grp.add
-        if dyd is None:              # (callers whose producer of dy is a LayerNorm backward get the masked copy from that launch)
-            dyd = _drop_bwd(dy, t_out)
-        gw2, gb2 = wgrad(dyd, h, alpha=scale, bias_grad=True)
-        stream2 = chain and ops.FFN2_BWD and ops.ffn2_shape_ok(dyd, w1, act) and z.is_contiguous()
-        if stream2:
-            # the block's own LayerNorm backward is dn's only reader: it sums the launch's partials itself (no finishing launch)
-            slab_ok = (ops.FFN2_BWD_LN and lng is not None and lng.takes(*x.shape) and (out_drop is None or ops.LN_BWD_DROP)
-                       and x.is_contiguous())
-            dz, dn = ops.ffn2_bwd_dx(dyd, scale, w1, w2, z, act, t_in, sum_dn=not slab_ok)
-        else:
-            dz = ops.linear_dx_drop(dyd, w2, t_in, alpha=scale, DZ=z, dact=act)    # inner mask and act'(z) in the epilogue
-        gw1, gb1 = wgrad(dz, n, bias_grad=True)
-        if not stream2:
-            dn = ops.linear_dx(dz, w1)
-        if out_drop is not None and lng is not None:       # + dx under the NEXT block's outer mask, from the same launch
-            dx, gln_w, gln_b, dxd = lng.bwd(dn, x, mean, rstd, ln_w, dx_add=dy, drop=out_drop)
-            return dx, (gln_w, gln_b, gw1, gb1, gw2, gb2), dxd
-        ln_bwd = ops.layernorm_bwd if lng is None else lng.bwd      # lng: the node's shared (dgamma, dbeta) reduction
-        dx, gln_w, gln_b = ln_bwd(dn, x, mean, rstd, ln_w, dx_add=dy)
-        return dx, (gln_w, gln_b, gw1, gb1, gw2, gb2)
-
-
+# the positional chain of the attention branch's backward with the layer's weight gradients, beside the chain (read here at call
+# time and passed down as ``lazy``: tests flip it on this module)
 _POS_DW_BESIDE = os.environ.get("TAVSR_POS_DW_BESIDE", "1") != "0"
-
-
-class _AttnFused:
-    """Attention core on the fused kernels (ops.attn_fwd / attn_bwd): scores, rel_shift, mask, softmax, dropout and the
-    context product in one launch; only the per-row log-sum-exp is kept for the backward, which recomputes the
-    probabilities.  q / k / v are 2-D row buffers with element offsets of their column windows (as _SelfAttnCore)."""
-
-    @staticmethod
-    def fwd(q, q_off, kbuf, k_off, vbuf, v_off, B, T1, T2, H, dk, klens, causal, pos=None, bias_u=None, bias_v=None,
-            p_att=0.0):
-        ctx, lse, tok = ops.attn_fwd(q, q_off, kbuf, k_off, vbuf, v_off, B, T1, T2, H, dk, klens=klens, causal=causal,
-                                     pos=pos, bias_u=bias_u, bias_v=bias_v, p_drop=p_att)
-        return ctx, (lse, tok)
-
-    @staticmethod
-    def bwd(dctx, ctx, saved, q, q_off, kbuf, k_off, vbuf, v_off, dq, dq_off, dk_buf, dk_off, dv_buf, dv_off, B, T1, T2, H,
-            dk, klens, causal, pos=None, bias_u=None, bias_v=None, lazy_dp=False):
-        """writes d/d(q+u) into dq, dK, dV into their windows; rel-pos: returns (dqv, dp) with dp the gradient of the
-        projected positional rows [2*T1-1, H*dk].  ``lazy_dp``: dp comes back as a function that computes it (two launches whose only
-        reader is linear_pos's weight gradient: the caller may run them with its other weight gradients, off the backward chain)."""
-        lse, tok = saved
-        dqv, sk = ops.attn_bwd(dctx, ctx, lse, tok, q, q_off, kbuf, k_off, vbuf, v_off, B, T1, T2, H, dk, dq, dq_off,
-                               dk_buf, dk_off, dv_buf, dv_off, klens=klens, causal=causal, pos=pos, bias_u=bias_u,
-                               bias_v=bias_v)
-        if pos is None:
-            return None, None
-        D = H * dk
-        W, Wp = 2 * T1 - 1, sk.shape[-1]
-
-        def make_dp():
-            # dP[:,h] = sum_b ds_skew[h,b]^T (q + v)[b,:,h]  == one K = B*T1 GEMM per head
-            _, qv = ops.add_head_bias(q[:, q_off: q_off + D], bias_u, bias_v)
-            dp = ops.empty(W, D, like=dctx)
-            ops.gemm(W, dk, B * T1, sk, Wp, qv, D, dp, D, a_kmajor=True, b_kmajor=True, nb1=H, sA=(B * T1 * Wp, 0),
-                     sB=(dk, 0), sC=(dk, 0))
-            return dp
-        return dqv, (make_dp if lazy_dp else make_dp())
-
-
-class _SelfAttnCore:
-    """Scores/softmax/context of one attention call on head-strided buffers.
-
-    q rows live in ``qbuf`` (row stride ldq, element offset q_off), k/v likewise; outputs go to
-    ``ctx`` [B*T1, D].  rel-pos (espnet RelPositionMultiHeadedAttention) when ``p`` is given."""
-
-    @staticmethod
-    def fwd(qu, ldq, q_off, kbuf, ldk, k_off, vbuf, ldv, v_off, B, T1, T2, H, dk, klens, causal, qv=None, p=None,
-            p_att=0.0):
-        D = H * dk
-        dev = qu
-        S = ops.pad4(T2)   # padded score-row stride: 16-byte loads in the GEMMs that read the scores
-        ac = ops.empty(H, B, T1, S, like=dev)
-        # ac[h,b] = Qu[b,:,h] K[b,:,h]^T
-        ops.gemm(T1, T2, dk, qu, ldq, kbuf, ldk, ac, S, a_off=q_off, b_off=k_off, nb1=B, nb2=H,
-                 sA=(T1 * ldq, dk), sB=(T2 * ldk, dk), sC=(T1 * S, B * T1 * S))
-        bd = None
-        W = 0
-        if p is not None:
-            W = 2 * T1 - 1
-            Wp = ops.pad4(W)
-            bd = ops.empty(H, B, T1, Wp, like=dev)
-            ops.gemm(T1, W, dk, qv, D, p, D, bd, Wp, nb1=B, nb2=H, sA=(T1 * D, dk), sB=(0, dk),
-                     sC=(T1 * Wp, B * T1 * Wp))
-        if p_att and p_att > 0.0:      # dropout on the probabilities (espnet forward_attention) by the softmax launch itself;
-            attn, pv, tok = ops.softmax_fwd(ac, bd, klens, 1.0 / math.sqrt(dk), causal, T2=T2, W=W, p_drop=p_att)
-            tok = (tok, pv)            # attn is kept; the dropped probabilities stay resident for dV (5 MB per layer)
-        else:
-            attn = ops.softmax_fwd(ac, bd, klens, 1.0 / math.sqrt(dk), causal, T2=T2, W=W)
-            pv, tok = attn, None
-        ctx = ops.empty(B * T1, D, like=dev)
-        # ctx[b,:,h] = drop(attn)[h,b] V[b,:,h]
-        ops.gemm(T1, dk, T2, pv, S, vbuf, ldv, ctx, D, b_off=v_off, b_kmajor=True, nb1=B, nb2=H,
-                 sA=(T1 * S, B * T1 * S), sB=(T2 * ldv, dk), sC=(T1 * D, dk))
-        return ctx, attn, tok
-
-    @staticmethod
-    def bwd(dctx, attn, qu, ldq, q_off, kbuf, ldk, k_off, vbuf, ldv, v_off, dq, lddq, dq_off, dk_buf, lddk, dk_off,
-            dv_buf, lddv, dv_off, B, T1, T2, H, dk, qv=None, p=None, tok=None):
-        """Writes dQ(u) into dq, dK into dk_buf, dV into dv_buf (head-strided); returns (dqv, dp) for rel-pos."""
-        D = H * dk
-        S = attn.shape[-1]
-        sS = (T1 * S, B * T1 * S)
-        dattn = torch.empty_like(attn)
-        # dattn[h,b] = dctx[b,:,h] V[b,:,h]^T
-        ops.gemm(T1, T2, dk, dctx, D, vbuf, ldv, dattn, S, b_off=v_off, nb1=B, nb2=H, sA=(T1 * D, dk),
-                 sB=(T2 * ldv, dk), sC=sS)
-        # dV[b,:,h] = drop(attn)[h,b]^T dctx[b,:,h]
-        pv = attn if tok is None else tok[1]
-        ops.gemm(T2, dk, T1, pv, S, dctx, D, dv_buf, lddv, c_off=dv_off, a_kmajor=True, b_kmajor=True, nb1=B, nb2=H,
-                 sA=sS, sB=(T1 * D, dk), sC=(T2 * lddv, dk))
-        del pv
-        # dattn is the gradient of the dropped probabilities: the softmax backward regenerates the mask itself
-        ds, sk = ops.softmax_bwd(attn, dattn, 1.0 / math.sqrt(dk), skew=p is not None, T2=T2,
-                                 token=None if tok is None else tok[0])
-        # dQu[b,:,h] = ds[h,b] K[b,:,h]
-        ops.gemm(T1, dk, T2, ds, S, kbuf, ldk, dq, lddq, b_off=k_off, c_off=dq_off, b_kmajor=True, nb1=B, nb2=H,
-                 sA=sS, sB=(T2 * ldk, dk), sC=(T1 * lddq, dk))
-        # dK[b,:,h] = ds[h,b]^T Qu[b,:,h]
-        ops.gemm(T2, dk, T1, ds, S, qu, ldq, dk_buf, lddk, b_off=q_off, c_off=dk_off, a_kmajor=True, b_kmajor=True,
-                 nb1=B, nb2=H, sA=sS, sB=(T1 * ldq, dk), sC=(T2 * lddk, dk))
-        if p is None:
-            return None, None
-        W = 2 * T1 - 1
-        Wp = sk.shape[-1]
-        dqv = ops.empty(B * T1, D, like=dctx)
-        # dQv[b,:,h] = ds_skew[h,b] P[:,h]
-        ops.gemm(T1, dk, W, sk, Wp, p, D, dqv, D, b_kmajor=True, nb1=B, nb2=H, sA=(T1 * Wp, B * T1 * Wp), sB=(0, dk),
-                 sC=(T1 * D, dk))
-        # dP[:,h] = sum_b ds_skew[h,b]^T Qv[b,:,h]  == one K = B*T1 GEMM per head
-        dp = ops.empty(W, D, like=dctx)
-        ops.gemm(W, dk, B * T1, sk, Wp, qv, D, dp, D, a_kmajor=True, b_kmajor=True, nb1=H, sA=(B * T1 * Wp, 0),
-                 sB=(dk, 0), sC=(dk, 0))
-        return dqv, dp
 
 
 # ------------------------------------------------------------------------------------------------
 # Branchformer encoder layer
 # ------------------------------------------------------------------------------------------------
-# parameter order of BranchformerLayerFn (None entries allowed for absent branches)
-BF_PARAM_NAMES = (
-    "norm_ff_macaron.weight", "norm_ff_macaron.bias",
-    "feed_forward_macaron.w_1.weight", "feed_forward_macaron.w_1.bias",
-    "feed_forward_macaron.w_2.weight", "feed_forward_macaron.w_2.bias",
-    "norm_mha.weight", "norm_mha.bias",
-    "attn.linear_q.weight", "attn.linear_q.bias", "attn.linear_k.weight", "attn.linear_k.bias",
-    "attn.linear_v.weight", "attn.linear_v.bias", "attn.linear_out.weight", "attn.linear_out.bias",
-    "attn.linear_pos.weight", "attn.pos_bias_u", "attn.pos_bias_v",
-    "norm_mlp.weight", "norm_mlp.bias",
-    "cgmlp.channel_proj1.0.weight", "cgmlp.channel_proj1.0.bias",
-    "cgmlp.csgu.norm.weight", "cgmlp.csgu.norm.bias", "cgmlp.csgu.conv.weight", "cgmlp.csgu.conv.bias",
-    "cgmlp.channel_proj2.weight", "cgmlp.channel_proj2.bias",
-    "pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias", "pooling_proj2.bias",
-    "weight_proj1.weight", "weight_proj2.weight", "weight_proj1.bias", "weight_proj2.bias",
-    "merge_proj.weight", "merge_proj.bias",
-    "norm_ff.weight", "norm_ff.bias",
-    "feed_forward.w_1.weight", "feed_forward.w_1.bias", "feed_forward.w_2.weight", "feed_forward.w_2.bias",
-    "norm_final.weight", "norm_final.bias",
+# the eight parameters of the learned-average merge in the order ops.merge_fwd / merge_bwd take them and the C descriptors'
+# ``merge_p`` / ``g_merge_p`` arrays hold them
+MERGE_PARAMS = ("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias", "pooling_proj2.bias",
+                "weight_proj1.weight", "weight_proj2.weight", "weight_proj1.bias", "weight_proj2.bias")
+
+# Every parameter of the layer, once: (name, field of tavsr_bf_layer_desc, gradient field of tavsr_bf_layer_bwd_desc).  No forward
+# field: the merge parameters (``merge_p``); no gradient field: those, and the five d_model LayerNorms, whose gradients come back
+# in one buffer (``g_ln``, _BWD_NORMS).  The tailored stream's descriptor has the same fields except for its one branch norm
+# (``br_ln_w`` / ``br_ln_b``: functional_av._ts_c_desc).
+_BF_PARAMS = (
+    ("norm_ff_macaron.weight", "ffm_ln_w", None), ("norm_ff_macaron.bias", "ffm_ln_b", None),
+    ("feed_forward_macaron.w_1.weight", "ffm_w1", "g_ffm_w1"), ("feed_forward_macaron.w_1.bias", "ffm_b1", "g_ffm_b1"),
+    ("feed_forward_macaron.w_2.weight", "ffm_w2", "g_ffm_w2"), ("feed_forward_macaron.w_2.bias", "ffm_b2", "g_ffm_b2"),
+    ("norm_mha.weight", "mha_ln_w", None), ("norm_mha.bias", "mha_ln_b", None),
+    ("attn.linear_q.weight", "wq", "g_wq"), ("attn.linear_q.bias", "bq", "g_bq"),
+    ("attn.linear_k.weight", "wk", "g_wk"), ("attn.linear_k.bias", "bk", "g_bk"),
+    ("attn.linear_v.weight", "wv", "g_wv"), ("attn.linear_v.bias", "bv", "g_bv"),
+    ("attn.linear_out.weight", "wo", "g_wo"), ("attn.linear_out.bias", "bo", "g_bo"),
+    ("attn.linear_pos.weight", "wpos", "g_wpos"), ("attn.pos_bias_u", "pos_u", "g_pos_u"), ("attn.pos_bias_v", "pos_v", "g_pos_v"),
+    ("norm_mlp.weight", "mlp_ln_w", None), ("norm_mlp.bias", "mlp_ln_b", None),
+    ("cgmlp.channel_proj1.0.weight", "cg_w1", "g_cg_w1"), ("cgmlp.channel_proj1.0.bias", "cg_b1", "g_cg_b1"),
+    ("cgmlp.csgu.norm.weight", "csgu_ln_w", "g_csgu_ln_w"), ("cgmlp.csgu.norm.bias", "csgu_ln_b", "g_csgu_ln_b"),
+    ("cgmlp.csgu.conv.weight", "csgu_cw", "g_csgu_cw"), ("cgmlp.csgu.conv.bias", "csgu_cb", "g_csgu_cb"),
+    ("cgmlp.channel_proj2.weight", "cg_w2", "g_cg_w2"), ("cgmlp.channel_proj2.bias", "cg_b2", "g_cg_b2"),
+    *((n, None, None) for n in MERGE_PARAMS),
+    ("merge_proj.weight", "merge_w", "g_merge_w"), ("merge_proj.bias", "merge_b", "g_merge_b"),
+    ("norm_ff.weight", "ff_ln_w", None), ("norm_ff.bias", "ff_ln_b", None),
+    ("feed_forward.w_1.weight", "ff_w1", "g_ff_w1"), ("feed_forward.w_1.bias", "ff_b1", "g_ff_b1"),
+    ("feed_forward.w_2.weight", "ff_w2", "g_ff_w2"), ("feed_forward.w_2.bias", "ff_b2", "g_ff_b2"),
+    ("norm_final.weight", "final_ln_w", None), ("norm_final.bias", "final_ln_b", None),
 )
+# parameter order of BranchformerLayerFn (None entries allowed for absent branches): the calling convention of cached_params
+BF_PARAM_NAMES = tuple(n for n, _, _ in _BF_PARAMS)
+DESC_FIELD = {n: f for n, f, _ in _BF_PARAMS if f is not None}                 # parameter -> field of the forward descriptor
+_DESC_PARAMS = tuple((f, n) for n, f, _ in _BF_PARAMS if f is not None)
+_BWD_FIELDS = tuple((g, n) for n, _, g in _BF_PARAMS if g is not None)          # gradient slot -> parameter
 _I = {n: i for i, n in enumerate(BF_PARAM_NAMES)}
-
-
-_LAYER_WS = {}
 
 
 def _layer_c_ok(x, cfg, P, pd, pos_emb=None) -> bool:
@@ -293,26 +112,6 @@ def _layer_c_ok(x, cfg, P, pd, pos_emb=None) -> bool:
             and bool(ops.lib().tavsr_branchformer_layer_ok(B, T, D, cfg["heads"], w1.shape[0], 2 * cw.shape[0], cw.shape[-1])))
 
 
-_DESC_PARAMS = (("ffm_ln_w", "norm_ff_macaron.weight"), ("ffm_ln_b", "norm_ff_macaron.bias"),
-                ("ffm_w1", "feed_forward_macaron.w_1.weight"), ("ffm_b1", "feed_forward_macaron.w_1.bias"),
-                ("ffm_w2", "feed_forward_macaron.w_2.weight"), ("ffm_b2", "feed_forward_macaron.w_2.bias"),
-                ("mha_ln_w", "norm_mha.weight"), ("mha_ln_b", "norm_mha.bias"),
-                ("wq", "attn.linear_q.weight"), ("bq", "attn.linear_q.bias"), ("wk", "attn.linear_k.weight"),
-                ("bk", "attn.linear_k.bias"), ("wv", "attn.linear_v.weight"), ("bv", "attn.linear_v.bias"),
-                ("wpos", "attn.linear_pos.weight"), ("pos_u", "attn.pos_bias_u"), ("pos_v", "attn.pos_bias_v"),
-                ("wo", "attn.linear_out.weight"), ("bo", "attn.linear_out.bias"),
-                ("mlp_ln_w", "norm_mlp.weight"), ("mlp_ln_b", "norm_mlp.bias"),
-                ("cg_w1", "cgmlp.channel_proj1.0.weight"), ("cg_b1", "cgmlp.channel_proj1.0.bias"),
-                ("csgu_ln_w", "cgmlp.csgu.norm.weight"), ("csgu_ln_b", "cgmlp.csgu.norm.bias"),
-                ("csgu_cw", "cgmlp.csgu.conv.weight"), ("csgu_cb", "cgmlp.csgu.conv.bias"),
-                ("cg_w2", "cgmlp.channel_proj2.weight"), ("cg_b2", "cgmlp.channel_proj2.bias"),
-                ("merge_w", "merge_proj.weight"), ("merge_b", "merge_proj.bias"),
-                ("ff_ln_w", "norm_ff.weight"), ("ff_ln_b", "norm_ff.bias"),
-                ("ff_w1", "feed_forward.w_1.weight"), ("ff_b1", "feed_forward.w_1.bias"),
-                ("ff_w2", "feed_forward.w_2.weight"), ("ff_b2", "feed_forward.w_2.bias"),
-                ("final_ln_w", "norm_final.weight"), ("final_ln_b", "norm_final.bias"))
-_DESC_MERGE = ("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias", "pooling_proj2.bias",
-               "weight_proj1.weight", "weight_proj2.weight", "weight_proj1.bias", "weight_proj2.bias")
 _DESC_TMPL = {}       # id(parameter list of a layer) -> (storage addresses, descriptor bytes with the parameter fields filled)
 _LAYER_LAYOUT = {}    # shape key -> ({buffer: (offset, shape)}, floats): the kept state of one layer as ONE allocation
 
@@ -346,6 +145,18 @@ def _layer_layout(B, T, D, H, N1, C2, need):
     return lay
 
 
+class _MergeSaved(NamedTuple):
+    """kept by the layer's merge and tail: the learned average's scores, its pooled vectors / row dots and the two weights
+    [B, 2] (all ``None`` for the other merge forms), the merged rows ``m`` (merge_proj's input; ``None`` from the one-launch tail
+    without ``save``) and the tokens of the concat buffer's dropout and of the tail's."""
+    score: Any
+    pooled: Any
+    wts: Any
+    m: Any
+    t_cat: Any
+    t_m: Any
+
+
 def _layer_sv(flat, off, x2d, toks, wts):
     """the kept state as the tensors the Python sequencing keeps (views of the one allocation)"""
     def g(k):
@@ -357,13 +168,15 @@ def _layer_sv(flat, off, x2d, toks, wts):
         for v in shp:
             n *= v
         return flat[o: o + n].view(shp)
-    return {"ffm": (x2d, g("ffm_mean"), g("ffm_rstd"), g("ffm_n"), g("ffm_z"), g("ffm_h"), toks[0], toks[1]),
-            "attn": (g("br_mean"), g("br_rstd"), g("n_mha"), g("qkv"), g("pp"), None, None, g("cx"), (g("lse"), toks[2]), None, toks[3]),
-            "mlp": (g("br_mean"), g("br_rstd"), g("n_mlp"), g("g"), g("g_z"), g("gn"), g("g_mean"), g("g_rstd"), g("u"), g("conv"),
-                    toks[4], toks[5]),
-            "merge": (g("score"), g("pooled"), wts, g("m")),
-            "drop": (None, toks[6]),
-            "ff": (g("x2"), g("ff_mean"), g("ff_rstd"), g("ff_n"), g("ff_z"), g("ff_h"), toks[7], toks[8]),
+    return {"ffm": FFNSaved(x=x2d, mean=g("ffm_mean"), rstd=g("ffm_rstd"), n=g("ffm_n"), z=g("ffm_z"), h=g("ffm_h"), t_in=toks[0],
+                            t_out=toks[1]),
+            "attn": AttnSaved(mean=g("br_mean"), rstd=g("br_rstd"), n=g("n_mha"), qkv=g("qkv"), pp=g("pp"), qu=None, qv=None, cx=g("cx"),
+                              attn=(g("lse"), toks[2]), t_att=None, t_br=toks[3]),
+            "mlp": CgmlpSaved(mean=g("br_mean"), rstd=g("br_rstd"), n=g("n_mlp"), g=g("g"), z=g("g_z"), gn=g("gn"), gmean=g("g_mean"),
+                              grstd=g("g_rstd"), u=g("u"), conv=g("conv"), t_u=toks[4], t_br=toks[5]),
+            "merge": _MergeSaved(score=g("score"), pooled=g("pooled"), wts=wts, m=g("m"), t_cat=None, t_m=toks[6]),
+            "ff": FFNSaved(x=g("x2"), mean=g("ff_mean"), rstd=g("ff_rstd"), n=g("ff_n"), z=g("ff_z"), h=g("ff_h"), t_in=toks[7],
+                           t_out=toks[8]),
             "final": (g("x3"), g("fin_mean"), g("fin_rstd")),
             "x1": g("x1"), "xa": g("xa"), "xm": g("xm")}
 
@@ -379,6 +192,43 @@ class _LazySV:
         if self._sv is None:
             self._sv = _layer_sv(self.flat, self.off, self.x2d, self.toks, self.wts)
         return self._sv[k]
+
+
+# ---- plumbing of the C sequencers' descriptors (tavsr_bf_layer_desc, tavsr_tailored_stream_desc / _layer_desc)
+def _draw_tokens(d, rates, sizes, device):
+    """the dropout tokens of a C-side forward, drawn in the order the Python sequencing draws them (same masks either way) and
+    written into the descriptor's ``drop_off`` / ``seed``; None where the rate is 0"""
+    toks = [ops._new_token(r, n, device) if r and r > 0.0 else None for r, n in zip(rates, sizes)]
+    for j, t in enumerate(toks):
+        if t is not None:
+            d.drop_off[j] = t[1]
+            d.seed = ops._addr(t[2])
+    return toks
+
+
+def _side_queue(d):
+    """``stream2`` / ``ev_fork`` / ``ev_join`` of a descriptor: the calling stream's side queue and fork / join events (one queue:
+    the calling stream itself - the events then order nothing new) -> (calling stream, side queue)"""
+    main = torch.cuda.current_stream()
+    side = ops.branch_stream(main) if ops.forks_enabled() else main
+    ev = ops.branch_events(main)
+    d.stream2, d.ev_fork, d.ev_join = side.cuda_stream, ev[0].cuda_event, ev[1].cuda_event
+    return main, side
+
+
+_WS_FLOATS = {}       # (entry point, shape key) -> floats of workspace the library asks for
+
+
+def _workspace(d, query, key, like):
+    """``ws`` / ``ws_floats`` of a descriptor: the size is asked of the library (entry point ``query``) once per shape key, the
+    block is allocated per call and returned (the caller keeps it until its launches are enqueued)"""
+    import ctypes as C
+    nws = _WS_FLOATS.get((query, key))
+    if nws is None:
+        nws = _WS_FLOATS[(query, key)] = getattr(ops.lib(), query)(C.byref(d))
+    ws = ops.empty(max(nws, 4), like=like)
+    d.ws, d.ws_floats = ops._addr(ws), nws
+    return ws
 
 
 def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
@@ -401,7 +251,7 @@ def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
         t = BfLayerDesc()
         for f, n in _DESC_PARAMS:
             setattr(t, f, sig[_I[n]])
-        for j, n in enumerate(_DESC_MERGE):
+        for j, n in enumerate(MERGE_PARAMS):
             t.merge_p[j] = sig[_I[n]]
         tm = _DESC_TMPL[id(P)] = (sig, bytes(t))
     d = BfLayerDesc.from_buffer_copy(tm[1])
@@ -409,17 +259,10 @@ def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
     d.ffn_act, d.save = ops.ACT[cfg["ffn_act"]], int(need)
     d.p_drop, d.p_att, d.coeff = pd, pa, cfg.get("coeff", 1.0)
     d.x, d.pos_emb, d.lens = ops._addr(x2d), ops._addr(pos_emb), ops._addr(lens)
-    # dropout tokens in the order the Python sequencing draws them (same masks either way)
     toks = [None] * 9
     if pd > 0.0 or pa > 0.0:
-        T4 = ops.pad4(T)
-        sizes = (M * N1, M * D, B * H * T * T4, M * D, M * Cn, M * D, M * D, M * N1, M * D)
-        rates = (pd, pd, pa, pd, pd, pd, pd, pd, pd)
-        toks = [ops._new_token(r, n, x.device) if r and r > 0.0 else None for r, n in zip(rates, sizes)]
-        for j, t in enumerate(toks):
-            if t is not None:
-                d.drop_off[j] = t[1]
-                d.seed = ops._addr(t[2])
+        sizes = (M * N1, M * D, B * H * T * ops.pad4(T), M * D, M * Cn, M * D, M * D, M * N1, M * D)
+        toks = _draw_tokens(d, (pd, pd, pa, pd, pd, pd, pd, pd, pd), sizes, x.device)
     off, nfl = _layer_layout(B, T, D, H, N1, C2, bool(need))
     flat = ops.empty(nfl, like=x)
     y = ops.empty(M, D, like=x)
@@ -428,16 +271,8 @@ def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
     for k, (o, _) in off.items():
         setattr(d, k, base + 4 * o)
     d.y, d.wts = ops._addr(y), ops._addr(wts)
-    main = torch.cuda.current_stream()
-    side = ops.branch_stream(main) if ops.forks_enabled() else main      # (one queue: the fork / join events order nothing new)
-    ev = ops.branch_events(main)
-    d.stream2, d.ev_fork, d.ev_join = side.cuda_stream, ev[0].cuda_event, ev[1].cuda_event
-    key = (B, T, D, H, N1, C2, int(need), pd > 0.0, pa > 0.0)
-    nws = _LAYER_WS.get(key)
-    if nws is None:
-        nws = _LAYER_WS[key] = lib().tavsr_branchformer_layer_ws(C.byref(d))
-    ws = ops.empty(max(nws, 4), like=x)
-    d.ws, d.ws_floats = ops._addr(ws), nws
+    main, _ = _side_queue(d)
+    ws = _workspace(d, "tavsr_branchformer_layer_ws", (B, T, D, H, N1, C2, int(need), pd > 0.0, pa > 0.0), x)
     check(lib().tavsr_branchformer_layer_fwd(C.byref(d), main.cuda_stream), "tavsr_branchformer_layer_fwd")
     ctx.sv, ctx.cfg, ctx.P, ctx.lens, ctx.pos_emb = _LazySV(flat, off, x2d, toks, wts), cfg, P, lens, pos_emb
     ctx.shape = (B, T, D)
@@ -449,22 +284,7 @@ def _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need):
     return y.view(B, T, D)
 
 
-# gradient slot of tavsr_bf_layer_bwd_desc -> parameter (BF_PARAM_NAMES); the five d_model LayerNorms come back in one buffer
-_BWD_FIELDS = (
-    ("g_ffm_w1", "feed_forward_macaron.w_1.weight"), ("g_ffm_b1", "feed_forward_macaron.w_1.bias"),
-    ("g_ffm_w2", "feed_forward_macaron.w_2.weight"), ("g_ffm_b2", "feed_forward_macaron.w_2.bias"),
-    ("g_wq", "attn.linear_q.weight"), ("g_bq", "attn.linear_q.bias"), ("g_wk", "attn.linear_k.weight"), ("g_bk", "attn.linear_k.bias"),
-    ("g_wv", "attn.linear_v.weight"), ("g_bv", "attn.linear_v.bias"), ("g_wo", "attn.linear_out.weight"), ("g_bo", "attn.linear_out.bias"),
-    ("g_wpos", "attn.linear_pos.weight"), ("g_pos_u", "attn.pos_bias_u"), ("g_pos_v", "attn.pos_bias_v"),
-    ("g_cg_w1", "cgmlp.channel_proj1.0.weight"), ("g_cg_b1", "cgmlp.channel_proj1.0.bias"),
-    ("g_csgu_ln_w", "cgmlp.csgu.norm.weight"), ("g_csgu_ln_b", "cgmlp.csgu.norm.bias"),
-    ("g_csgu_cw", "cgmlp.csgu.conv.weight"), ("g_csgu_cb", "cgmlp.csgu.conv.bias"),
-    ("g_cg_w2", "cgmlp.channel_proj2.weight"), ("g_cg_b2", "cgmlp.channel_proj2.bias"),
-    ("g_merge_w", "merge_proj.weight"), ("g_merge_b", "merge_proj.bias"),
-    ("g_ff_w1", "feed_forward.w_1.weight"), ("g_ff_b1", "feed_forward.w_1.bias"),
-    ("g_ff_w2", "feed_forward.w_2.weight"), ("g_ff_b2", "feed_forward.w_2.bias"))
-_BWD_MERGE = ("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias", "pooling_proj2.bias",
-              "weight_proj1.weight", "weight_proj2.weight", "weight_proj1.bias", "weight_proj2.bias")
+# the five d_model LayerNorms, whose (dgamma, dbeta) pairs come back in one buffer, in its order
 _BWD_NORMS = ("norm_final", "norm_ff", "norm_mlp", "norm_mha", "norm_ff_macaron")
 
 
@@ -485,7 +305,7 @@ def _grad_layout(P, D):
                 k *= v
             ent.append((_I[n], f, o, k, shp))
             o += (k + 63) // 64 * 64
-        for j, n in enumerate(_BWD_MERGE):
+        for j, n in enumerate(MERGE_PARAMS):
             shp = shapes[_I[n]]
             k = 1
             for v in shp:
@@ -510,10 +330,7 @@ def _layer_c_backward(ctx, dy):
     B, T, D = ctx.shape
     M = B * T
     dy2 = dy.contiguous().view(M, D)
-    main = torch.cuda.current_stream()
-    side = ops.branch_stream(main) if ops.forks_enabled() else main
-    ev = ops.branch_events(main)
-    d.stream2, d.ev_fork, d.ev_join = side.cuda_stream, ev[0].cuda_event, ev[1].cuda_event
+    main, side = _side_queue(d)
     b = BfLayerBwdDesc()
     b.fwd = C.pointer(d)
     _, ent, ln0, nfl = _grad_layout(P, D)
@@ -530,12 +347,7 @@ def _layer_c_backward(ctx, dy):
             setattr(b, f, base + 4 * o)
     dx = ops.empty(M, D, like=dy2)
     b.dy, b.dx, b.g_ln = ops._addr(dy2), ops._addr(dx), base + 4 * ln0
-    key = ("bwd", B, T, D, d.H, d.ffn_units, d.cg_units, d.p_drop > 0.0)
-    nws = _LAYER_WS.get(key)
-    if nws is None:
-        nws = _LAYER_WS[key] = lib().tavsr_branchformer_layer_bwd_ws(C.byref(b))
-    ws = ops.empty(max(nws, 4), like=dy2)
-    b.ws, b.ws_floats = ops._addr(ws), nws
+    ws = _workspace(b, "tavsr_branchformer_layer_bwd_ws", (B, T, D, d.H, d.ffn_units, d.cg_units, d.p_drop > 0.0), dy2)
     beside = side is not main and ops.WGRAD_SLOT == 0 and ops.wgrad_may_go_beside(P) and ops.wgrad_open(main, side)
     b.wgrad_beside = 1 if beside else 0
     check(lib().tavsr_branchformer_layer_bwd(C.byref(b), main.cuda_stream), "tavsr_branchformer_layer_bwd")
@@ -548,6 +360,82 @@ def _layer_c_backward(ctx, dy):
     return (dx.view(B, T, D), None, None, None, *G)
 
 
+def _bf_branch_out(h, w, b, cat, off, pd, rowdot):
+    """a branch's output projection -> (branch output, its dropout token, the merge's row dots of it): into the branch's half of
+    the concat buffer (masked later, both halves in one call), or with the dropout - x1 = dropout(x_att), x2 = dropout(x2):
+    encoder_layer.py:212,224 - and, for the fused tail, the merge's row dots in the launch's epilogue"""
+    if cat is not None:
+        ops.linear(h, w, b, out=cat, out_off=off, ldc=cat.shape[1])
+        return cat[:, off: off + w.shape[0]], None, None
+    if rowdot is not None and ops.rowdot_ok(h, w):
+        return ops.linear_drop(h, w, b, pd, rowdot=rowdot)
+    return (*ops.linear_drop(h, w, b, pd), None)
+
+
+def _bf_merge_fwd(p, cfg, xa, xm, cat, x1, mp, rowdots, lens, B, T, need):
+    """the layer behind the branch join: the merge (learned average | fixed average | concat | the one branch there is) and the
+    tail x1 + coeff * dropout(merge_proj(m)) - as one launch with the learned average where the kernel takes the shape, with an
+    identity merge_proj for a single-branch layer (encoder_layer.py:232-309) -> (x2, _MergeSaved)"""
+    merge, pd, coeff = cfg["merge"], cfg.get("p", 0.0), cfg.get("coeff", 1.0)
+    D = x1.shape[1]
+    t_cat = _drop_(cat, pd) if cat is not None else None      # both halves in one call (iid)
+    score = pooled = wts = x2 = None
+    if mp is not None:
+        if not cfg["merge_identity"] and ops.merge_proj_ok(xa, xm, p["merge_proj.weight"], T, D, res=x1):
+            # merge + merge_proj + dropout + residual: the whole tail behind the join as ONE launch
+            score, pooled, wts, m, x2, t_m = ops.merge_proj_fwd(xa, xm, lens, mp, p["merge_proj.weight"], p["merge_proj.bias"], x1, coeff,
+                                                                pd, B, T, save=need, rowdots=rowdots)
+        else:
+            score, pooled, wts, m = ops.merge_fwd(xa, xm, lens, mp, B, T)       # pooling + weighted sum: one launch for T <= 128
+    elif xa is not None and xm is not None and merge == "fixed_ave":
+        cw = cfg["cgmlp_weight"]
+        m = ops.axpby(xa, xm, 1.0 - cw, cw)
+    elif xa is not None and xm is not None and merge == "concat":
+        m = cat
+    else:
+        m = xa if xa is not None else xm
+    if x2 is not None:
+        pass                                            # (the fused tail above)
+    elif cfg["merge_identity"]:
+        t_m, md = None, m
+        if pd > 0.0:                                    # x + coeff * dropout(x1 | x2)  (encoder_layer.py:302-309)
+            md, t_m = ops.dropout(m.contiguous(), pd)
+        x2 = ops.axpby(x1, md, 1.0, coeff)
+    else:                                               # x + coeff * dropout(merge_proj(.))  (:232-300)
+        x2, t_m = ops.linear_drop(m, p["merge_proj.weight"], p["merge_proj.bias"], pd, alpha=coeff, res=x1)
+    return x2, _MergeSaved(score=score, pooled=pooled, wts=wts, m=m, t_cat=t_cat, t_m=t_m)
+
+
+def _bf_merge_bwd(p, cfg, sv, dx2, dxd, lens, B, T, grp, G):
+    """backward of _bf_merge_fwd from dx2 (``dxd``: dx2 under the tail's mask, where the LayerNorm backward above wrote it) ->
+    (dxa, dxm, masked): the gradients of the two branch outputs (None for an absent branch), and whether they already are under the
+    branch outputs' dropout masks (the learned average's backward applies them itself: no mask launches at the head of the
+    branches)"""
+    ms, coeff, merge = sv["merge"], cfg.get("coeff", 1.0), cfg["merge"]
+    has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
+    two = has_attn and has_mlp
+    if cfg["merge_identity"]:
+        dm = ops.axpby(dx2, None, coeff, 0.0) if (coeff != 1.0 or ms.t_m is not None) else dx2
+        _drop_bwd_(dm, ms.t_m)
+    else:       # merge projection: x2 = x1 + coeff * (m Wm^T + bm)
+        dxd = _drop_bwd(dx2, ms.t_m) if dxd is None else dxd
+        G["merge_proj.weight"], G["merge_proj.bias"] = grp.add(dxd, ms.m, alpha=coeff, bias_grad=True)
+        dm = ops.linear_dx(dxd, p["merge_proj.weight"], alpha=coeff)
+    if two and merge == "learned_ave":
+        dxa, dxm, mg = ops.merge_bwd(dm, sv["xa"], sv["xm"], lens, [p[k] for k in MERGE_PARAMS], ms.score, ms.pooled, ms.wts, B, T,
+                                     drop1=sv["attn"].t_br, drop2=sv["mlp"].t_br)
+        G.update((k, g.view_as(p[k])) for k, g in zip(MERGE_PARAMS, mg))
+        return dxa, dxm, True
+    if two and merge == "fixed_ave":
+        cw = cfg["cgmlp_weight"]
+        return ops.axpby(dm, None, 1.0 - cw, 0.0), ops.axpby(dm, None, cw, 0.0), False
+    if two and merge == "concat":
+        D = dx2.shape[1]
+        _drop_bwd_(dm, ms.t_cat)
+        return dm[:, :D], dm[:, D:], False
+    return (dm if has_attn else None), (dm if has_mlp else None), False
+
+
 class BranchformerLayerFn(torch.autograd.Function):
     """``MyBranchformerEncoderLayer.forward`` (src/encoder/branchformer/encoder_layer.py:153-321) with
     dropout / stochastic depth disabled (rate 0 or eval); ``coeff`` is the stochastic-depth scale."""
@@ -555,146 +443,48 @@ class BranchformerLayerFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, pos_emb, lens, cfg, *P):
         need = _note_ctx(ctx)
-        B, T, D = x.shape
-        M = B * T
-        H = cfg["heads"]
-        dk = D // H
-        act = cfg["ffn_act"]
-        merge = cfg["merge"]  # learned_ave | fixed_ave | concat | attn_only | mlp_only (+ identity flag)
-        has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
-        coeff = cfg.get("coeff", 1.0)
-        pd, pa = cfg.get("p", 0.0), cfg.get("p_att", 0.0)     # dropout rates (0 in eval)
-        p = lambda n: P[_I[n]]
+        pd = cfg.get("p", 0.0)                                # dropout rate (0 in eval)
         if _layer_c_ok(x, cfg, P, pd, pos_emb):
             return _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need)
-        x2d = x.reshape(M, D)
-        sv = {}
-
-        # the macaron block's finishing launch also normalises its output for the two branches (one statistics pass)
-        br_norms = ([(p("norm_mha.weight"), p("norm_mha.bias"))] if has_attn else []) + \
-                   ([(p("norm_mlp.weight"), p("norm_mlp.bias"))] if has_mlp else [])
-        x1, sv["ffm"], nbr, bmean, brstd = _FFN.fwd_ln(x2d, p("norm_ff_macaron.weight"), p("norm_ff_macaron.bias"),
-                                                       p("feed_forward_macaron.w_1.weight"), p("feed_forward_macaron.w_1.bias"),
-                                                       p("feed_forward_macaron.w_2.weight"), p("feed_forward_macaron.w_2.bias"),
-                                                       act, 0.5, br_norms, p=pd, save=need)
+        B, T, D = x.shape
+        M = B * T
+        p = dict(zip(BF_PARAM_NAMES, P))
+        act, merge = cfg["ffn_act"], cfg["merge"]             # learned_ave | fixed_ave | concat (+ identity flag for one branch)
+        has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
         two = has_attn and has_mlp
+        sv = {}
+        # the macaron block's finishing launch also normalises its output for the two branches (one statistics pass)
+        br_norms = ([(p["norm_mha.weight"], p["norm_mha.bias"])] if has_attn else []) + \
+                   ([(p["norm_mlp.weight"], p["norm_mlp.bias"])] if has_mlp else [])
+        x1, sv["ffm"], nbr, bmean, brstd = _FFN.fwd_ln(x.reshape(M, D), *[p[k] for k in FFM_PARAMS], act, 0.5, br_norms, p=pd, save=need)
         cat = ops.empty(M, 2 * D, like=x) if merge == "concat" else None
-        xa = xm = None
-        mp = rd = None
-        use_rd = False
-        if two and merge == "learned_ave":
-            mp = [p(k) for k in ("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias",
-                                 "pooling_proj2.bias", "weight_proj1.weight", "weight_proj2.weight",
-                                 "weight_proj1.bias", "weight_proj2.bias")]
-            rd = [None, None]
-            # the fused tail takes the merge's row dots from the epilogues of the launches that store the branch outputs
-            use_rd = (ops.MERGE_ROWDOT and not cfg["merge_identity"] and ops.MERGE_PROJ and ops.MERGE_ROWS
-                      and bool(ops.lib().tavsr_merge_proj_ok(T, D)))
+        mp = [p[k] for k in MERGE_PARAMS] if two and merge == "learned_ave" else None
+        # the fused tail takes the merge's row dots from the epilogues of the launches that store the branch outputs
+        use_rd = (mp is not None and ops.MERGE_ROWDOT and not cfg["merge_identity"] and ops.MERGE_PROJ and ops.MERGE_ROWS
+                  and bool(ops.lib().tavsr_merge_proj_ok(T, D)))
+        xa = xm = rd_a = rd_m = None
         br = ops.BranchScope(two)     # attention branch beside the cgMLP branch (joined before the merge)
         with br:
             if has_attn:
-                n, mean, rstd = nbr[0], bmean, brstd
-                qkv = ops.empty(M, 3 * D, like=x)
-                ops.linear_group(n, [(p(f"attn.linear_{c}.weight"), p(f"attn.linear_{c}.bias"), j * D)
-                                     for j, c in enumerate("qkv")], qkv)
-                pe2d = pos_emb.reshape(-1, D)
-                pp = ops.linear(pe2d, p("attn.linear_pos.weight"))
-                if ops.ATTN_FUSED and dk == 64:
-                    qu = qv = t_att = None
-                    cx, attn = _AttnFused.fwd(qkv, 0, qkv, D, qkv, 2 * D, B, T, T, H, dk, lens, False, pos=pp,
-                                              bias_u=p("attn.pos_bias_u").reshape(-1), bias_v=p("attn.pos_bias_v").reshape(-1),
-                                              p_att=pa)
-                else:
-                    qu, qv = ops.add_head_bias(qkv[:, :D], p("attn.pos_bias_u").reshape(-1), p("attn.pos_bias_v").reshape(-1))
-                    cx, attn, t_att = _SelfAttnCore.fwd(qu, D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, B, T, T, H, dk, lens, False,
-                                                        qv=qv, p=pp, p_att=pa)
-                t_xa = None
-                if merge == "concat":
-                    ops.linear(cx, p("attn.linear_out.weight"), p("attn.linear_out.bias"), out=cat, out_off=0, ldc=2 * D)
-                    xa = cat[:, :D]
-                else:
-                    wo_ = p("attn.linear_out.weight")
-                    if use_rd and ops.rowdot_ok(cx, wo_):     # ... and the merge's row dots of x1 from the same launch's epilogue
-                        xa, t_xa, rd[0] = ops.linear_drop(cx, wo_, p("attn.linear_out.bias"), pd, rowdot=(mp[0], mp[4]))
-                    else:
-                        xa, t_xa = ops.linear_drop(cx, wo_, p("attn.linear_out.bias"), pd)   # x1 = dropout(x_att)  (encoder_layer.py:212)
-                sv["attn"] = (mean, rstd, n, qkv, pp, qu, qv, cx, attn, t_att, t_xa)
+                cx, s = AttnBranch.fwd(nbr[0], p, pos_emb, lens, B, T, cfg["heads"], cfg.get("p_att", 0.0))
+                xa, t_xa, rd_a = _bf_branch_out(cx, p["attn.linear_out.weight"], p["attn.linear_out.bias"], cat, 0, pd,
+                                                (mp[0], mp[4]) if use_rd else None)
+                sv["attn"] = s._replace(mean=bmean, rstd=brstd, t_br=t_xa)
         if has_mlp:
-            n, mean, rstd = nbr[-1], bmean, brstd
-            w1c = p("cgmlp.channel_proj1.0.weight")
-            cw = p("cgmlp.csgu.conv.weight")
-            # channel_proj1's epilogue leaves the CSGU's LayerNorm statistics as per-tile row sums (no statistics launch)
-            rst = (ops.empty(M, w1c.shape[0] // 64, 2, like=x)
-                   if (ops.CSGU_FUSED and cw.shape[-1] == 31 and ops.csgu_rowstat_ok(n, w1c)) else None)
-            if need:
-                g, z = ops.linear(n, w1c, p("cgmlp.channel_proj1.0.bias"), act="gelu", save_z=True, rowstat=rst)
-            else:
-                g, z = ops.linear(n, w1c, p("cgmlp.channel_proj1.0.bias"), act="gelu", rowstat=rst), None
-            Cn = g.shape[1] // 2
-            if ops.csgu_usable(g, cw):       # LayerNorm + depthwise convolution + gate + dropout: one pass over g
-                u, conv, gn, gmean, grstd, t_u = ops.csgu_fwd(g, p("cgmlp.csgu.norm.weight"), p("cgmlp.csgu.norm.bias"), EPS_ESPNET,
-                                                              cw.reshape(Cn, -1), p("cgmlp.csgu.conv.bias"), B, T, p=pd, save=need,
-                                                              rowstat=rst)
-            else:
-                gn, gmean, grstd = ops.layernorm_fwd(g[:, Cn:], p("cgmlp.csgu.norm.weight"), p("cgmlp.csgu.norm.bias"),
-                                                     EPS_ESPNET)
-                u, conv = ops.dwconv_gate_fwd(gn, g[:, :Cn], cw.reshape(Cn, -1), p("cgmlp.csgu.conv.bias"), B, T)
-                t_u = _drop_(u, pd)                             # csgu: dropout(x_r * x_g)
-            t_xm = None
-            if merge == "concat":
-                ops.linear(u, p("cgmlp.channel_proj2.weight"), p("cgmlp.channel_proj2.bias"), out=cat, out_off=D,
-                           ldc=2 * D)
-                xm = cat[:, D:]
-            else:
-                w2_ = p("cgmlp.channel_proj2.weight")
-                if use_rd and ops.rowdot_ok(u, w2_):
-                    xm, t_xm, rd[1] = ops.linear_drop(u, w2_, p("cgmlp.channel_proj2.bias"), pd, rowdot=(mp[1], mp[5]))
-                else:
-                    xm, t_xm = ops.linear_drop(u, w2_, p("cgmlp.channel_proj2.bias"), pd)   # x2 = dropout(x2)  (encoder_layer.py:224)
-            sv["mlp"] = (mean, rstd, n, g, z, gn, gmean, grstd, u, conv, t_u, t_xm)
+            u, s = CgmlpBranch.fwd(nbr[-1], p, B, T, pd, need)
+            xm, t_xm, rd_m = _bf_branch_out(u, p["cgmlp.channel_proj2.weight"], p["cgmlp.channel_proj2.bias"], cat, D, pd,
+                                            (mp[1], mp[5]) if use_rd else None)
+            sv["mlp"] = s._replace(mean=bmean, rstd=brstd, t_br=t_xm)
         br.join()
-        t_cat = _drop_(cat, pd) if (merge == "concat" and cat is not None) else None   # both halves in one call (iid)
-        wts = None
-        x2 = None
-        if two and merge == "learned_ave":
-            if not cfg["merge_identity"] and ops.merge_proj_ok(xa, xm, p("merge_proj.weight"), T, D, res=x1):
-                # merge + merge_proj + dropout + residual: the whole tail behind the join as ONE launch
-                score, pooled, wts, m, x2, t_m = ops.merge_proj_fwd(xa, xm, lens, mp, p("merge_proj.weight"), p("merge_proj.bias"),
-                                                                    x1, coeff, pd, B, T, save=need,
-                                                                    rowdots=(rd[0], rd[1]) if rd[0] is not None and rd[1] is not None else None)
-            else:
-                score, pooled, wts, m = ops.merge_fwd(xa, xm, lens, mp, B, T)       # pooling + weighted sum: one launch for T <= 128
-            sv["merge"] = (score, pooled, wts, m)
-        elif two and merge == "fixed_ave":
-            cw_ = cfg["cgmlp_weight"]
-            m = ops.axpby(xa, xm, 1.0 - cw_, cw_)
-            sv["merge"] = (m,)
-        elif two and merge == "concat":
-            m = cat
-            sv["merge"] = (m,)
-        else:
-            m = xa if has_attn else xm
-            sv["merge"] = (m,)
-        if x2 is not None:
-            pass                                            # (the fused tail above)
-        elif cfg["merge_identity"]:
-            t_m = None
-            md = m
-            if pd > 0.0:                                    # x + coeff * dropout(x1 | x2)  (encoder_layer.py:302-309)
-                md, t_m = ops.dropout(m.contiguous(), pd)
-            x2 = ops.axpby(x1, md, 1.0, coeff)
-        else:                                               # x + coeff * dropout(merge_proj(.))  (:232-300)
-            x2, t_m = ops.linear_drop(m, p("merge_proj.weight"), p("merge_proj.bias"), pd, alpha=coeff, res=x1)
-        sv["drop"] = (t_cat, t_m)
-        x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, p("norm_ff.weight"), p("norm_ff.bias"), p("feed_forward.w_1.weight"),
-                                                       p("feed_forward.w_1.bias"), p("feed_forward.w_2.weight"),
-                                                       p("feed_forward.w_2.bias"), act, 0.5,
-                                                       [(p("norm_final.weight"), p("norm_final.bias"))], p=pd, save=need)
+        x2, sv["merge"] = _bf_merge_fwd(p, cfg, xa, xm, cat, x1, mp, (rd_a, rd_m) if rd_a is not None and rd_m is not None else None,
+                                        lens, B, T, need)
+        x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, *[p[k] for k in FF_PARAMS], act, 0.5,
+                                                       [(p["norm_final.weight"], p["norm_final.bias"])], p=pd, save=need)
         sv["final"] = (x3, fmean, frstd)
         sv["x1"], sv["xa"], sv["xm"] = x1, xa, xm
         ctx.sv, ctx.cfg, ctx.P, ctx.lens, ctx.pos_emb = sv, cfg, P, lens, pos_emb
         ctx.shape = (B, T, D)
-        cfg["_last_w"] = wts   # (weight_global, weight_local) for the introspection attributes
+        cfg["_last_w"] = sv["merge"].wts   # (weight_global, weight_local) for the introspection attributes
         return y.view(B, T, D)
 
     @staticmethod
@@ -705,153 +495,55 @@ class BranchformerLayerFn(torch.autograd.Function):
             return _layer_c_backward(ctx, dy)
         sv, cfg, P = ctx.sv, ctx.cfg, ctx.P
         B, T, D = ctx.shape
-        M = B * T
-        H = cfg["heads"]
-        dk = D // H
-        act, merge = cfg["ffn_act"], cfg["merge"]
+        act = cfg["ffn_act"]
         has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
-        coeff = cfg.get("coeff", 1.0)
-        two = has_attn and has_mlp
-        p = lambda n: P[_I[n]]
-        G: List[Optional[torch.Tensor]] = [None] * len(BF_PARAM_NAMES)
-
-        def put(name, g, like=None):
-            G[_I[name]] = g if like is None else g.view_as(like)
-
+        p = dict(zip(BF_PARAM_NAMES, P))
+        G = {}
         beside = ops.wgrad_may_go_beside(P)
-        pos_dw = pos_sums = None
         grp = ops.WgradGroup()     # every weight gradient of the layer in one grouped launch (flushed at the end)
         lng = ops.LNGroup()        # ... and the five d=256 LayerNorms' (dgamma, dbeta) partials in one reduction
-        dy2 = dy.contiguous().view(M, D)
         x3, fmean, frstd = sv["final"]
         # each LayerNorm backward whose dx the next block's dropout mask is applied to also writes the masked copy
-        t_m = sv["drop"][1]
-        t_ff, t_ffm = sv["ff"][-1], sv["ffm"][-1]
-        dx3, g1, g2, *dyd = lng.bwd(dy2, x3, fmean, frstd, p("norm_final.weight"), drop=t_ff)
-        put("norm_final.weight", g1); put("norm_final.bias", g2)
-        dx2, gs, *dxd = _FFN.bwd(dx3, sv["ff"], p("norm_ff.weight"), p("feed_forward.w_1.weight"),
-                                 p("feed_forward.w_2.weight"), act, 0.5, grp=grp, lng=lng, dyd=dyd[0] if dyd else None,
-                                 out_drop=None if cfg["merge_identity"] else t_m)
-        for n_, g in zip(("norm_ff.weight", "norm_ff.bias", "feed_forward.w_1.weight", "feed_forward.w_1.bias",
-                          "feed_forward.w_2.weight", "feed_forward.w_2.bias"), gs):
-            put(n_, g)
-        # merge projection: x2 = x1 + coeff * (m Wm^T + bm)
-        m = sv["merge"][-1]
-        t_cat = sv["drop"][0]
-        if cfg["merge_identity"]:
-            dm = ops.axpby(dx2, None, coeff, 0.0) if (coeff != 1.0 or t_m is not None) else dx2
-            _drop_bwd_(dm, t_m) if t_m is not None else None
-        else:
-            dxd = dxd[0] if dxd else _drop_bwd(dx2, t_m)
-            gw_, gb_ = grp.add(dxd, m, alpha=coeff, bias_grad=True)
-            put("merge_proj.weight", gw_); put("merge_proj.bias", gb_)
-            dm = ops.linear_dx(dxd, p("merge_proj.weight"), alpha=coeff)
-        xa, xm = sv["xa"], sv["xm"]
-        masked = False
-        if two and merge == "learned_ave":
-            score, pooled, wts, _ = sv["merge"]
-            mp = [p(k) for k in ("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias",
-                                 "pooling_proj2.bias", "weight_proj1.weight", "weight_proj2.weight",
-                                 "weight_proj1.bias", "weight_proj2.bias")]
-            # (dxa / dxm come back under the branch outputs' dropout masks: no mask launches at the head of the branches)
-            dxa, dxm, mg = ops.merge_bwd(dm, xa, xm, ctx.lens, mp, score, pooled, wts, B, T, drop1=sv["attn"][-1],
-                                         drop2=sv["mlp"][-1])
-            masked = True
-            for k, g in zip(("pooling_proj1.weight", "pooling_proj2.weight", "pooling_proj1.bias", "pooling_proj2.bias",
-                             "weight_proj1.weight", "weight_proj2.weight", "weight_proj1.bias", "weight_proj2.bias"), mg):
-                put(k, g, like=p(k))
-        elif two and merge == "fixed_ave":
-            cw_ = cfg["cgmlp_weight"]
-            dxa = ops.axpby(dm, None, 1.0 - cw_, 0.0)
-            dxm = ops.axpby(dm, None, cw_, 0.0)
-        elif two and merge == "concat":
-            _drop_bwd_(dm, t_cat)
-            dxa, dxm = dm[:, :D], dm[:, D:]
-        else:
-            dxa = dm if has_attn else None
-            dxm = dm if has_mlp else None
-
+        t_ffm = sv["ffm"].t_out
+        dx3, G["norm_final.weight"], G["norm_final.bias"], *dyd = lng.bwd(dy.contiguous().view(B * T, D), x3, fmean, frstd,
+                                                                         p["norm_final.weight"], drop=sv["ff"].t_out)
+        dx2, gs, *dxd = _FFN.bwd(dx3, sv["ff"], p["norm_ff.weight"], p["feed_forward.w_1.weight"], p["feed_forward.w_2.weight"], act, 0.5,
+                                 grp=grp, lng=lng, dyd=dyd[0] if dyd else None,
+                                 out_drop=None if cfg["merge_identity"] else sv["merge"].t_m)
+        G.update(zip(FF_PARAMS, gs))
+        dxa, dxm, masked = _bf_merge_bwd(p, cfg, sv, dx2, dxd[0] if dxd else None, ctx.lens, B, T, grp, G)
         x1 = sv["x1"]
         dx1 = dx2  # residual path; branch gradients are folded in through dx_add
-        br = ops.BranchScope(two)     # attention-branch backward beside the cgMLP-branch backward
-        dn_a = None
+        br = ops.BranchScope(has_attn and has_mlp)     # attention-branch backward beside the cgMLP-branch backward
+        late = ()
         with br:
             if has_attn:
-                a_mean, a_rstd, n, qkv, pp, qu, qv, cx, attn, t_att, t_xa = sv["attn"]
-                if t_xa is not None and not masked:
-                    dxa = _drop_bwd(dxa.contiguous(), t_xa)
-                gw_, gb_ = grp.add(dxa, cx, bias_grad=True)
-                put("attn.linear_out.weight", gw_); put("attn.linear_out.bias", gb_)
-                dcx = ops.linear_dx(dxa, p("attn.linear_out.weight"))
-                dqkv = torch.empty_like(qkv)
-                dqu = ops.empty(M, D, like=dy2)
-                if qu is None:       # fused attention core
-                    dqv, dp = _AttnFused.bwd(dcx, cx, attn, qkv, 0, qkv, D, qkv, 2 * D, dqu, 0, dqkv, D, dqkv, 2 * D, B, T, T,
-                                             H, dk, ctx.lens, False, pos=pp, bias_u=p("attn.pos_bias_u").reshape(-1),
-                                             bias_v=p("attn.pos_bias_v").reshape(-1), lazy_dp=beside and _POS_DW_BESIDE)
-                else:
-                    dqv, dp = _SelfAttnCore.bwd(dcx, attn, qu, D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, dqu, D, 0, dqkv, 3 * D, D,
-                                                dqkv, 3 * D, 2 * D, B, T, T, H, dk, qv=qv, p=pp, tok=t_att)
-                gu_, gv_, *late = ops.add2_colsum(dqu, dqv, dqkv[:, :D], lazy_sums=beside and _POS_DW_BESIDE)      # dQ = dQu + dQv and both bias gradients, one pass
-                pos_sums = late[0] if late else None
-                put("attn.pos_bias_u", gu_, like=p("attn.pos_bias_u"))
-                put("attn.pos_bias_v", gv_, like=p("attn.pos_bias_v"))
-                pe2d = ctx.pos_emb.reshape(-1, D)
-                if callable(dp):      # the positional rows' gradient and linear_pos's weight gradient (4 launches, ~55 us of the attention
-                    pos_dw = lambda dp=dp: put("attn.linear_pos.weight", ops.linear_dw(dp(), pe2d))      # branch): with the others, beside
-                else:
-                    put("attn.linear_pos.weight", ops.linear_dw(dp, pe2d))   # K = 2T-1: not a multiple of 32, stays alone
-                for j, nm in enumerate(("q", "k", "v")):   # three problems with their own outputs (no sliced gradients)
-                    gw_, gb_ = grp.add(dqkv[:, j * D:(j + 1) * D], n, bias_grad=True)
-                    put(f"attn.linear_{nm}.weight", gw_); put(f"attn.linear_{nm}.bias", gb_)
-                dn_a = ops.linear_dx_cat(dqkv, [p(f"attn.linear_{c}.weight") for c in "qkv"])    # one K = 3D GEMM
+                sa = sv["attn"]
+                if sa.t_br is not None and not masked:
+                    dxa = _drop_bwd(dxa.contiguous(), sa.t_br)
+                dn_a, late = AttnBranch.bwd(dxa, sa, p, ctx.pos_emb, ctx.lens, B, T, cfg["heads"], grp, G,
+                                            lazy=beside and _POS_DW_BESIDE)
         if has_mlp:
-            mean, rstd, n, g, z, gn, gmean, grstd, u, conv, t_u, t_xm = sv["mlp"]
-            Cn = g.shape[1] // 2
-            if t_xm is not None and not masked:
-                dxm = _drop_bwd(dxm.contiguous(), t_xm)
-            gw_, gb_ = grp.add(dxm, u, bias_grad=True)
-            put("cgmlp.channel_proj2.weight", gw_); put("cgmlp.channel_proj2.bias", gb_)
-            du = ops.linear_dx_drop(dxm, p("cgmlp.channel_proj2.weight"), t_u)
-            dg = torch.empty_like(g)
-            cw = p("cgmlp.csgu.conv.weight")
-            fused = ops.CGMLP_ACT_BWD_FUSED and cw.shape[-1] == 31      # gelu'(z) applied by the two kernels that write dg's halves
-            dgn, gcw, gcb = ops.dwconv_gate_bwd(du, gn, g[:, :Cn], conv, cw.reshape(Cn, -1), dg[:, :Cn], B, T,
-                                                zr=z[:, :Cn] if fused else None)
-            put("cgmlp.csgu.conv.weight", gcw, like=cw); put("cgmlp.csgu.conv.bias", gcb)
-            if fused:
-                _, g1, g2 = ops.layernorm_bwd_act(dgn, g[:, Cn:], gmean, grstd, p("cgmlp.csgu.norm.weight"), z[:, Cn:], "gelu",
-                                                  dx=dg[:, Cn:])
-            else:
-                _, g1, g2 = ops.layernorm_bwd(dgn, g[:, Cn:], gmean, grstd, p("cgmlp.csgu.norm.weight"), dx=dg[:, Cn:])
-            put("cgmlp.csgu.norm.weight", g1); put("cgmlp.csgu.norm.bias", g2)
-            if not fused:
-                ops.act_bwd_(dg, z, "gelu")
-            gw_, gb_ = grp.add(dg, n, bias_grad=True)
-            put("cgmlp.channel_proj1.0.weight", gw_); put("cgmlp.channel_proj1.0.bias", gb_)
-            dn = ops.linear_dx(dg, p("cgmlp.channel_proj1.0.weight"))
-            dx1, g1, g2, *dyd = lng.bwd(dn, x1, mean, rstd, p("norm_mlp.weight"), dx_add=dx1, drop=None if has_attn else t_ffm)
-            put("norm_mlp.weight", g1); put("norm_mlp.bias", g2)
+            sm = sv["mlp"]
+            if sm.t_br is not None and not masked:
+                dxm = _drop_bwd(dxm.contiguous(), sm.t_br)
+            dn = CgmlpBranch.bwd(dxm, sm, p, B, T, grp, G)
+            dx1, G["norm_mlp.weight"], G["norm_mlp.bias"], *dyd = lng.bwd(dn, x1, sm.mean, sm.rstd, p["norm_mlp.weight"], dx_add=dx1,
+                                                                          drop=None if has_attn else t_ffm)
         br.join()
         if has_attn:     # same accumulation order into dx1 as a single stream: cgMLP branch first, then attention
-            dx1, g1, g2, *dyd = lng.bwd(dn_a, x1, a_mean, a_rstd, p("norm_mha.weight"), dx_add=dx1, drop=t_ffm)
-            put("norm_mha.weight", g1); put("norm_mha.bias", g2)
-        dx, gs = _FFN.bwd(dx1, sv["ffm"], p("norm_ff_macaron.weight"), p("feed_forward_macaron.w_1.weight"),
-                          p("feed_forward_macaron.w_2.weight"), act, 0.5, grp=grp, lng=lng, dyd=dyd[0] if dyd else None)
-        for n_, g in zip(("norm_ff_macaron.weight", "norm_ff_macaron.bias", "feed_forward_macaron.w_1.weight",
-                          "feed_forward_macaron.w_1.bias", "feed_forward_macaron.w_2.weight",
-                          "feed_forward_macaron.w_2.bias"), gs):
-            put(n_, g)
-        for i, prm in enumerate(P):
-            if prm is None:
-                G[i] = None
-        if beside:       # no reader before the end of the pass: beside the next layer's chain
-            ops.wgrad_beside(lambda: (pos_sums() if pos_sums else None, pos_dw() if pos_dw else None, grp.flush(), lng.flush()))
+            dx1, G["norm_mha.weight"], G["norm_mha.bias"], *dyd = lng.bwd(dn_a, x1, sa.mean, sa.rstd, p["norm_mha.weight"], dx_add=dx1,
+                                                                          drop=t_ffm)
+        dx, gs = _FFN.bwd(dx1, sv["ffm"], p["norm_ff_macaron.weight"], p["feed_forward_macaron.w_1.weight"],
+                          p["feed_forward_macaron.w_2.weight"], act, 0.5, grp=grp, lng=lng, dyd=dyd[0] if dyd else None)
+        G.update(zip(FFM_PARAMS, gs))
+        if beside:       # no reader before the end of the pass: beside the next layer's chain (the positional chain first)
+            ops.wgrad_beside(lambda: ([f() for f in late], grp.flush(), lng.flush()))
         else:
             grp.flush()
             lng.flush()
         ctx.sv = None
-        return (dx.view(B, T, D), None, None, None, *G)
+        return (dx.view(B, T, D), None, None, None, *[None if prm is None else G.get(n) for n, prm in zip(BF_PARAM_NAMES, P)])
 
 
 # ------------------------------------------------------------------------------------------------

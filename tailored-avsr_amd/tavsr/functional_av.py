@@ -12,7 +12,9 @@ import torch
 
 from . import ops
 from ._lib import guarded
-from .functional import EPS_ESPNET, _FFN, _AttnFused, _SelfAttnCore, _drop_, _drop_bwd, _drop_bwd_, _note_ctx
+from .functional import DESC_FIELD, _draw_tokens, _note_ctx, _side_queue, _workspace
+from .layer_blocks import (EPS_ESPNET, FF_PARAMS, FFM_PARAMS, AttnBranch, AttnSaved, CgmlpBranch, CgmlpSaved, FFNSaved, _FFN, _drop_,
+                           _drop_bwd)
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1   # torch.nn.BatchNorm defaults (conv3d_resnet18.py:57, resnet.py:39,68,84)
 
@@ -326,118 +328,39 @@ def tailored_stream_param_names(use_attn: bool):
 
 def _ts_branch_fwd(p, cfg, x1, n, mean, rstd, pos_emb, lens, B, T, need):
     """the stream's attention OR cgMLP branch with its residual (src/encoder/audiovisual/tailored/encoder_layer.py:185-208,
-    232-256) on the already normalised rows ``n``: returns (x2, saved)."""
-    M, D = x1.shape
-    H = cfg["heads"]
-    dk = D // H
-    coeff = cfg.get("coeff", 1.0)
-    pd, pa = cfg.get("p", 0.0), cfg.get("p_att", 0.0)      # dropout rates (0 in eval)
+    232-256) on the already normalised rows ``n``: returns (x2, saved).  The output projection carries the branch's dropout and
+    the residual in its epilogue: x2 = x1 + coeff * dropout(branch)  (encoder_layer.py:196,208,243,256)."""
+    coeff, pd = cfg.get("coeff", 1.0), cfg.get("p", 0.0)      # dropout rates: 0 in eval
     if cfg["use_attn"]:
-        qkv = ops.empty(M, 3 * D, like=x1)
-        ops.linear_group(n, [(p[f"attn.linear_{c}.weight"], p[f"attn.linear_{c}.bias"], j * D) for j, c in enumerate("qkv")],
-                         qkv)
-        pp = ops.linear(pos_emb.reshape(-1, D), p["attn.linear_pos.weight"])
-        if ops.ATTN_FUSED and dk == 64:
-            qu = qv = t_att = None
-            cx, attn = _AttnFused.fwd(qkv, 0, qkv, D, qkv, 2 * D, B, T, T, H, dk, lens, False, pos=pp,
-                                      bias_u=p["attn.pos_bias_u"].reshape(-1), bias_v=p["attn.pos_bias_v"].reshape(-1),
-                                      p_att=pa)
-        else:
-            qu, qv = ops.add_head_bias(qkv[:, :D], p["attn.pos_bias_u"].reshape(-1), p["attn.pos_bias_v"].reshape(-1))
-            cx, attn, t_att = _SelfAttnCore.fwd(qu, D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, B, T, T, H, dk, lens, False,
-                                                qv=qv, p=pp, p_att=pa)
-        # residual + coeff * dropout(att)  (encoder_layer.py:196,243): the dropout rides in the GEMM epilogue
+        cx, s = AttnBranch.fwd(n, p, pos_emb, lens, B, T, cfg["heads"], cfg.get("p_att", 0.0))
         x2, t_br = ops.linear_drop(cx, p["attn.linear_out.weight"], p["attn.linear_out.bias"], pd, alpha=coeff, res=x1)
-        return x2, (mean, rstd, n, qkv, pp, qu, qv, cx, attn, t_att, t_br)
-    w1c = p["cgmlp.channel_proj1.0.weight"]
-    cw = p["cgmlp.csgu.conv.weight"]
+        return x2, s._replace(mean=mean, rstd=rstd, t_br=t_br)
+    w1c, cw = p["cgmlp.channel_proj1.0.weight"], p["cgmlp.csgu.conv.weight"]
     if ops.BLOCKS_C and ops.cgmlp_block_ok(n, w1c, cw) and x1.is_contiguous():      # the whole branch as one C call
         x2, (g, z, gn, gmean, grstd, u, conv, t_u, t_br), _ = ops.cgmlp_fwd(
             n, w1c, p["cgmlp.channel_proj1.0.bias"], p["cgmlp.csgu.norm.weight"], p["cgmlp.csgu.norm.bias"], cw,
             p["cgmlp.csgu.conv.bias"], p["cgmlp.channel_proj2.weight"], p["cgmlp.channel_proj2.bias"], B, T, p=pd, p_out=pd, alpha=coeff,
             res=x1, save=need)
-        return x2, (mean, rstd, n, g, z, gn, gmean, grstd, u, conv, t_u, t_br)
-    # channel_proj1's epilogue leaves the CSGU's LayerNorm statistics as per-tile row sums (no statistics launch)
-    rst = (ops.empty(n.shape[0], w1c.shape[0] // 64, 2, like=n)
-           if (ops.CSGU_FUSED and cw.shape[-1] == 31 and ops.csgu_rowstat_ok(n, w1c)) else None)
-    if need:
-        g, z = ops.linear(n, w1c, p["cgmlp.channel_proj1.0.bias"], act="gelu", save_z=True, rowstat=rst)
-    else:
-        g, z = ops.linear(n, w1c, p["cgmlp.channel_proj1.0.bias"], act="gelu", rowstat=rst), None
-    Cn = g.shape[1] // 2
-    if ops.csgu_usable(g, cw):         # LayerNorm + depthwise convolution + gate + dropout: one pass over g
-        u, conv, gn, gmean, grstd, t_u = ops.csgu_fwd(g, p["cgmlp.csgu.norm.weight"], p["cgmlp.csgu.norm.bias"], EPS_ESPNET,
-                                                      cw.reshape(Cn, -1), p["cgmlp.csgu.conv.bias"], B, T, p=pd, save=need,
-                                                      rowstat=rst)
-    else:
-        gn, gmean, grstd = ops.layernorm_fwd(g[:, Cn:], p["cgmlp.csgu.norm.weight"], p["cgmlp.csgu.norm.bias"], EPS_ESPNET)
-        u, conv = ops.dwconv_gate_fwd(gn, g[:, :Cn], cw.reshape(Cn, -1), p["cgmlp.csgu.conv.bias"], B, T)
-        t_u = _drop_(u, pd)            # csgu: dropout(x_r * x_g)
-    # residual + coeff * dropout(cgmlp)  (encoder_layer.py:208,256)
+        return x2, CgmlpSaved(mean=mean, rstd=rstd, n=n, g=g, z=z, gn=gn, gmean=gmean, grstd=grstd, u=u, conv=conv, t_u=t_u, t_br=t_br)
+    u, s = CgmlpBranch.fwd(n, p, B, T, pd, need)
     x2, t_br = ops.linear_drop(u, p["cgmlp.channel_proj2.weight"], p["cgmlp.channel_proj2.bias"], pd, alpha=coeff, res=x1)
-    return x2, (mean, rstd, n, g, z, gn, gmean, grstd, u, conv, t_u, t_br)
+    return x2, s._replace(mean=mean, rstd=rstd, t_br=t_br)
 
 
 def _ts_branch_bwd(p, cfg, saved, dx2, x1, pos_emb, lens, B, T, grp, lng, G, dbr=None, out_drop=None):
     """backward of _ts_branch_fwd: returns dx1 (the residual path included) and fills ``G`` with the branch's gradients.
     ``dbr``: dx2 under the branch's outer mask when the caller's LayerNorm backward already produced it; ``out_drop``: the
     token of the block below - the branch's own LayerNorm backward then also returns dx1 under that mask (dx1, dx1_masked)."""
-    M, D = x1.shape
-    H = cfg["heads"]
-    dk = D // H
     coeff = cfg.get("coeff", 1.0)
+    dbr = _drop_bwd(dx2, saved.t_br) if dbr is None else dbr
     if cfg["use_attn"]:
-        mean, rstd, n, qkv, pp, qu, qv, cx, attn, t_att, t_br = saved
-        dbr = _drop_bwd(dx2, t_br) if dbr is None else dbr
-        G["attn.linear_out.weight"], G["attn.linear_out.bias"] = grp.add(dbr, cx, alpha=coeff, bias_grad=True)
-        dcx = ops.linear_dx(dbr, p["attn.linear_out.weight"], alpha=coeff)
-        dqkv = torch.empty_like(qkv)
-        dqu = ops.empty(M, D, like=dx2)
-        if qu is None:           # fused attention core
-            dqv, dp = _AttnFused.bwd(dcx, cx, attn, qkv, 0, qkv, D, qkv, 2 * D, dqu, 0, dqkv, D, dqkv, 2 * D, B, T, T, H, dk,
-                                     lens, False, pos=pp, bias_u=p["attn.pos_bias_u"].reshape(-1),
-                                     bias_v=p["attn.pos_bias_v"].reshape(-1))
-        else:
-            dqv, dp = _SelfAttnCore.bwd(dcx, attn, qu, D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, dqu, D, 0, dqkv, 3 * D, D,
-                                        dqkv, 3 * D, 2 * D, B, T, T, H, dk, qv=qv, p=pp, tok=t_att)
-        gu_, gv_ = ops.add2_colsum(dqu, dqv, dqkv[:, :D])
-        G["attn.pos_bias_u"], G["attn.pos_bias_v"] = gu_.view_as(p["attn.pos_bias_u"]), gv_.view_as(p["attn.pos_bias_v"])
-        G["attn.linear_pos.weight"] = ops.linear_dw(dp, pos_emb.reshape(-1, D))
-        for j, nm in enumerate(("q", "k", "v")):
-            G[f"attn.linear_{nm}.weight"], G[f"attn.linear_{nm}.bias"] = grp.add(dqkv[:, j * D:(j + 1) * D], n, bias_grad=True)
-        dn = ops.linear_dx_cat(dqkv, [p[f"attn.linear_{c}.weight"] for c in "qkv"])      # one K = 3D GEMM
-        dx1, G["norm_mha.weight"], G["norm_mha.bias"], *dxd = lng.bwd(dn, x1, mean, rstd, p["norm_mha.weight"], dx_add=dx2,
-                                                                      drop=out_drop)
-        return (dx1, dxd[0]) if dxd else dx1
-    mean, rstd, n, g, z, gn, gmean, grstd, u, conv, t_u, t_br = saved
-    Cn = g.shape[1] // 2
-    dbr = _drop_bwd(dx2, t_br) if dbr is None else dbr
-    G["cgmlp.channel_proj2.weight"], G["cgmlp.channel_proj2.bias"] = grp.add(dbr, u, alpha=coeff, bias_grad=True)
-    du = ops.linear_dx_drop(dbr, p["cgmlp.channel_proj2.weight"], t_u, alpha=coeff)
-    dg = torch.empty_like(g)
-    cw = p["cgmlp.csgu.conv.weight"]
-    fused = ops.CGMLP_ACT_BWD_FUSED and cw.shape[-1] == 31      # gelu'(z) applied by the two kernels that write dg's halves
-    dgn, gcw, gcb = ops.dwconv_gate_bwd(du, gn, g[:, :Cn], conv, cw.reshape(Cn, -1), dg[:, :Cn], B, T,
-                                        zr=z[:, :Cn] if fused else None)
-    G["cgmlp.csgu.conv.weight"], G["cgmlp.csgu.conv.bias"] = gcw.view_as(cw), gcb
-    if fused:
-        _, G["cgmlp.csgu.norm.weight"], G["cgmlp.csgu.norm.bias"] = ops.layernorm_bwd_act(
-            dgn, g[:, Cn:], gmean, grstd, p["cgmlp.csgu.norm.weight"], z[:, Cn:], "gelu", dx=dg[:, Cn:])
+        bn = "norm_mha"
+        dn, _ = AttnBranch.bwd(dbr, saved, p, pos_emb, lens, B, T, cfg["heads"], grp, G, alpha=coeff)
     else:
-        _, G["cgmlp.csgu.norm.weight"], G["cgmlp.csgu.norm.bias"] = ops.layernorm_bwd(
-            dgn, g[:, Cn:], gmean, grstd, p["cgmlp.csgu.norm.weight"], dx=dg[:, Cn:])
-        ops.act_bwd_(dg, z, "gelu")
-    G["cgmlp.channel_proj1.0.weight"], G["cgmlp.channel_proj1.0.bias"] = grp.add(dg, n, bias_grad=True)
-    dn = ops.linear_dx(dg, p["cgmlp.channel_proj1.0.weight"])
-    dx1, G["norm_cgmlp.weight"], G["norm_cgmlp.bias"], *dxd = lng.bwd(dn, x1, mean, rstd, p["norm_cgmlp.weight"], dx_add=dx2,
-                                                                      drop=out_drop)
+        bn = "norm_cgmlp"
+        dn = CgmlpBranch.bwd(dbr, saved, p, B, T, grp, G, alpha=coeff)
+    dx1, G[bn + ".weight"], G[bn + ".bias"], *dxd = lng.bwd(dn, x1, saved.mean, saved.rstd, p[bn + ".weight"], dx_add=dx2, drop=out_drop)
     return (dx1, dxd[0]) if dxd else dx1
-
-
-_FFM = ("norm_ff_macaron.weight", "norm_ff_macaron.bias", "feed_forward_macaron.w_1.weight", "feed_forward_macaron.w_1.bias",
-        "feed_forward_macaron.w_2.weight", "feed_forward_macaron.w_2.bias")
-_FF = ("norm_ff.weight", "norm_ff.bias", "feed_forward.w_1.weight", "feed_forward.w_1.bias", "feed_forward.w_2.weight",
-       "feed_forward.w_2.bias")
 
 
 class TailoredStreamFn(torch.autograd.Function):
@@ -453,10 +376,10 @@ class TailoredStreamFn(torch.autograd.Function):
         x2d = x.contiguous().view(M, D)
         sv = {}
         bn = "norm_mha" if cfg["use_attn"] else "norm_cgmlp"     # the branch's LayerNorm rides in the macaron block's finishing launch
-        x1, sv["ffm"], (n,), mean, rstd = _FFN.fwd_ln(x2d, *[p[k] for k in _FFM], act, 0.5, [(p[bn + ".weight"], p[bn + ".bias"])],
+        x1, sv["ffm"], (n,), mean, rstd = _FFN.fwd_ln(x2d, *[p[k] for k in FFM_PARAMS], act, 0.5, [(p[bn + ".weight"], p[bn + ".bias"])],
                                                       p=pd, save=need)
         x2, sv["br"] = _ts_branch_fwd(p, cfg, x1, n, mean, rstd, pos_emb, lens, B, T, need)
-        x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, *[p[k] for k in _FF], act, 0.5,
+        x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, *[p[k] for k in FF_PARAMS], act, 0.5,
                                                        [(p["norm_final.weight"], p["norm_final.bias"])], p=pd, save=need)
         sv["final"] = (x3, fmean, frstd)
         sv["x1"] = x1
@@ -475,20 +398,20 @@ class TailoredStreamFn(torch.autograd.Function):
         lng = ops.LNGroup()        # the stream's four d-wide LayerNorms: one (dgamma, dbeta) reduction
         x3, fmean, frstd = sv["final"]
         # (each LayerNorm backward also writes its dx under the outer mask of the block below: no stand-alone mask launches)
-        t_ff, t_br, t_ffm = sv["ff"][-1], sv["br"][-1], sv["ffm"][-1]
+        t_ff, t_br, t_ffm = sv["ff"].t_out, sv["br"].t_br, sv["ffm"].t_out
         dx3, G["norm_final.weight"], G["norm_final.bias"], *dyd = lng.bwd(dy.contiguous().view(M, D), x3, fmean, frstd,
                                                                          p["norm_final.weight"], drop=t_ff)
         # chain=False: the two modality streams run side by side (measured on the AV step: 367.9 utt/s with the dgrad GEMMs,
         # 365.3 with the streaming launch, which cannot share the chip with the other stream's kernels)
         dx2, gs, *dbr = _FFN.bwd(dx3, sv["ff"], p["norm_ff.weight"], p["feed_forward.w_1.weight"], p["feed_forward.w_2.weight"], act,
                                  0.5, grp=grp, lng=lng, chain=False, dyd=dyd[0] if dyd else None, out_drop=t_br)
-        G.update(zip(_FF, gs))
+        G.update(zip(FF_PARAMS, gs))
         dx1 = _ts_branch_bwd(p, cfg, sv["br"], dx2, sv["x1"], ctx.pos_emb, ctx.lens, B, T, grp, lng, G,
                              dbr=dbr[0] if dbr else None, out_drop=t_ffm)
         dx1, dyd = dx1 if isinstance(dx1, tuple) else (dx1, None)
         dx, gs = _FFN.bwd(dx1, sv["ffm"], p["norm_ff_macaron.weight"], p["feed_forward_macaron.w_1.weight"],
                           p["feed_forward_macaron.w_2.weight"], act, 0.5, grp=grp, lng=lng, chain=False, dyd=dyd)
-        G.update(zip(_FFM, gs))
+        G.update(zip(FFM_PARAMS, gs))
         grp.flush()        # (on the side queue, un-joined, as the Branchformer layer does: 380 -> 375 utt/s on the AV step - the two modality
         lng.flush()        # streams already share the chip, and the second stream's side queue is a third queue)
         ctx.sv = None
@@ -498,9 +421,6 @@ class TailoredStreamFn(torch.autograd.Function):
 # (One feed-forward call for BOTH modality streams - the shared FFNs as one [Ma + Mv, 256] problem, SURVEY a9 - was built and
 # measured in round 3: 363.5-364.3 utt/s against 367.2-367.5 per stream on the batch-32 AV step, profiles/r03_notes.md section 3;
 # the per-stream form keeps two launch queues whose kernels fill each other's prologue / finishing phases.  Removed in round 4.)
-
-
-_TS_WS = {}
 
 
 def _ts_c_ok(x, cfg, p) -> bool:
@@ -520,8 +440,7 @@ def _ts_c_ok(x, cfg, p) -> bool:
 def _ts_c_desc(ns, x, pos_emb, lens, cfg, p, names, need):
     """descriptor + buffers of one stream for tavsr_tailored_layer_fwd; leaves ``ns`` exactly as TailoredStreamFn.forward does
     (the Python backward runs on it).  Draws the stream's dropout tokens in the order of the Python sequencing."""
-    from ._lib import TailoredStreamDesc, lib
-    import ctypes as C
+    from ._lib import TailoredStreamDesc
     B, T, D = x.shape
     M, H = B * T, cfg["heads"]
     N1 = p["feed_forward.w_1.weight"].shape[0]
@@ -533,36 +452,21 @@ def _ts_c_desc(ns, x, pos_emb, lens, cfg, p, names, need):
     d = TailoredStreamDesc()
     d.B, d.T, d.D, d.H, d.ffn_units, d.ffn_act, d.save, d.use_attn = B, T, D, H, N1, ops.ACT[cfg["ffn_act"]], int(need), int(ua)
     d.p_drop, d.p_att, d.coeff = pd, pa, cfg.get("coeff", 1.0)
-    bn = "norm_mha" if ua else "norm_cgmlp"
-    fields = [("ffm_ln_w", "norm_ff_macaron.weight"), ("ffm_ln_b", "norm_ff_macaron.bias"), ("ffm_w1", "feed_forward_macaron.w_1.weight"),
-              ("ffm_b1", "feed_forward_macaron.w_1.bias"), ("ffm_w2", "feed_forward_macaron.w_2.weight"),
-              ("ffm_b2", "feed_forward_macaron.w_2.bias"), ("br_ln_w", bn + ".weight"), ("br_ln_b", bn + ".bias"),
-              ("ff_ln_w", "norm_ff.weight"), ("ff_ln_b", "norm_ff.bias"), ("ff_w1", "feed_forward.w_1.weight"), ("ff_b1", "feed_forward.w_1.bias"),
-              ("ff_w2", "feed_forward.w_2.weight"), ("ff_b2", "feed_forward.w_2.bias"), ("final_ln_w", "norm_final.weight"),
-              ("final_ln_b", "norm_final.bias")]
     if ua:
-        fields += [("wq", "attn.linear_q.weight"), ("bq", "attn.linear_q.bias"), ("wk", "attn.linear_k.weight"), ("bk", "attn.linear_k.bias"),
-                   ("wv", "attn.linear_v.weight"), ("bv", "attn.linear_v.bias"), ("wpos", "attn.linear_pos.weight"), ("pos_u", "attn.pos_bias_u"),
-                   ("pos_v", "attn.pos_bias_v"), ("wo", "attn.linear_out.weight"), ("bo", "attn.linear_out.bias")]
         sizes = (M * N1, M * D, B * H * T * ops.pad4(T), M * D, M * N1, M * D)
         rates = (pd, pd, pa, pd, pd, pd)
     else:
         C2 = p["cgmlp.channel_proj1.0.weight"].shape[0]
         Cn = C2 // 2
         d.cg_units, d.cg_kernel = C2, p["cgmlp.csgu.conv.weight"].shape[-1]
-        fields += [("cg_w1", "cgmlp.channel_proj1.0.weight"), ("cg_b1", "cgmlp.channel_proj1.0.bias"), ("csgu_ln_w", "cgmlp.csgu.norm.weight"),
-                   ("csgu_ln_b", "cgmlp.csgu.norm.bias"), ("csgu_cw", "cgmlp.csgu.conv.weight"), ("csgu_cb", "cgmlp.csgu.conv.bias"),
-                   ("cg_w2", "cgmlp.channel_proj2.weight"), ("cg_b2", "cgmlp.channel_proj2.bias")]
         sizes = (M * N1, M * D, M * Cn, M * D, M * N1, M * D)
         rates = (pd,) * 6
-    for f, n in fields:
+    bn = "norm_mha." if ua else "norm_cgmlp."      # the stream's one branch norm: the field the layer's descriptor names differently
+    for n in names:
+        f = ("br_ln_w" if n.endswith(".weight") else "br_ln_b") if n.startswith(bn) else DESC_FIELD[n]
         setattr(d, f, ops._addr(p[n]))
     d.x, d.pos_emb, d.lens = ops._addr(x2d), ops._addr(pos_emb), ops._addr(lens)
-    toks = [ops._new_token(r, n, x.device) if r and r > 0.0 else None for r, n in zip(rates, sizes)]
-    for j, t in enumerate(toks):
-        if t is not None:
-            d.drop_off[j] = t[1]
-            d.seed = ops._addr(t[2])
+    toks = _draw_tokens(d, rates, sizes, x.device)
     b = {k: E(M, D) for k in ("x1", "n_br", "x2", "x3", "y")}
     if ua:
         b.update(qkv=E(M, 3 * D), pp=E(2 * T - 1, D), cx=E(M, D), lse=E(B * H, T))
@@ -575,19 +479,19 @@ def _ts_c_desc(ns, x, pos_emb, lens, cfg, p, names, need):
         b.update({k: E(M) for k in ("ffm_mean", "ffm_rstd", "br_mean", "br_rstd", "ff_mean", "ff_rstd", "fin_mean", "fin_rstd")})
     for k, t in b.items():
         setattr(d, k, ops._addr(t))
-    key = (B, T, D, H, N1, int(ua), d.cg_units, int(need))
-    nws = _TS_WS.get(key)
-    if nws is None:
-        nws = _TS_WS[key] = lib().tavsr_tailored_stream_ws(C.byref(d))
-    ws = ops.empty(max(nws, 4), like=x)
-    d.ws, d.ws_floats = ops._addr(ws), nws
+    ws = _workspace(d, "tavsr_tailored_stream_ws", (B, T, D, H, N1, int(ua), d.cg_units, int(need)), x)
     g = b.get
     if ua:
-        br = (g("br_mean"), g("br_rstd"), b["n_br"], b["qkv"], b["pp"], None, None, b["cx"], (b["lse"], toks[2]), None, toks[3])
+        br = AttnSaved(mean=g("br_mean"), rstd=g("br_rstd"), n=b["n_br"], qkv=b["qkv"], pp=b["pp"], qu=None, qv=None, cx=b["cx"],
+                       attn=(b["lse"], toks[2]), t_att=None, t_br=toks[3])
     else:
-        br = (g("br_mean"), g("br_rstd"), b["n_br"], b["g"], g("g_z"), g("gn"), b["g_mean"], b["g_rstd"], b["u"], g("conv"), toks[2], toks[3])
-    sv = {"ffm": (x2d, g("ffm_mean"), g("ffm_rstd"), g("ffm_n"), g("ffm_z"), g("ffm_h"), toks[0], toks[1]), "br": br,
-          "ff": (b["x2"], g("ff_mean"), g("ff_rstd"), g("ff_n"), g("ff_z"), g("ff_h"), toks[4], toks[5]),
+        br = CgmlpSaved(mean=g("br_mean"), rstd=g("br_rstd"), n=b["n_br"], g=b["g"], z=g("g_z"), gn=g("gn"), gmean=b["g_mean"],
+                        grstd=b["g_rstd"], u=b["u"], conv=g("conv"), t_u=toks[2], t_br=toks[3])
+    sv = {"ffm": FFNSaved(x=x2d, mean=g("ffm_mean"), rstd=g("ffm_rstd"), n=g("ffm_n"), z=g("ffm_z"), h=g("ffm_h"), t_in=toks[0],
+                          t_out=toks[1]),
+          "br": br,
+          "ff": FFNSaved(x=b["x2"], mean=g("ff_mean"), rstd=g("ff_rstd"), n=g("ff_n"), z=g("ff_z"), h=g("ff_h"), t_in=toks[4],
+                         t_out=toks[5]),
           "final": (b["x3"], g("fin_mean"), g("fin_rstd")), "x1": b["x1"]}
     ns.sv, ns.cfg, ns.p, ns.names, ns.pos_emb, ns.shape, ns.lens = sv, cfg, p, names, pos_emb, (B, T, D), lens
     return d, ws, b["y"].view(B, T, D)
@@ -600,12 +504,9 @@ def _tailored_c_forward(ca, cv, audio, apos, alens, cfg_a, video, vpos, vlens, c
     import ctypes as C
     dv, wsv, yv = _ts_c_desc(cv, video, vpos, vlens, cfg_v, pv, names_v, need)      # (the Python sequencing draws the video stream's tokens first)
     da, wsa, ya = _ts_c_desc(ca, audio, apos, alens, cfg_a, pa, names_a, need)
-    main = torch.cuda.current_stream()
-    side = ops.branch_stream(main) if ops.forks_enabled() else main
-    ev = ops.branch_events(main)
     L = TailoredLayerDesc()
     L.audio, L.video = C.pointer(da), C.pointer(dv)
-    L.stream2, L.ev_fork, L.ev_join = side.cuda_stream, ev[0].cuda_event, ev[1].cuda_event
+    main, _ = _side_queue(L)
     check(lib().tavsr_tailored_layer_fwd(C.byref(L), main.cuda_stream), "tavsr_tailored_layer_fwd")
     return ya, yv
 

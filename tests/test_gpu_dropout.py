@@ -100,6 +100,58 @@ def test_model_backward_under_frozen_masks():
     assert abs(fd - gnorm) / gnorm < 3e-2, (fd, gnorm)
 
 
+MERGE_FORMS = [("learned_ave", 0.5, 0.0), ("fixed_ave", 0.3, 0.0), ("fixed_ave", 0.0, 0.0), ("fixed_ave", 1.0, 0.0), ("concat", 0.5, 0.0),
+               ("learned_ave", 0.5, 1.0)]
+
+
+@pytest.mark.parametrize("merge,cgmlp_weight,branch_drop", MERGE_FORMS)
+def test_encoder_layers_backward_under_frozen_masks(merge, cgmlp_weight, branch_drop):
+    """test_model_backward_under_frozen_masks at layer level, for every merge form of the Branchformer layer (the tails behind the
+    merge - the concat mask, the dropout of a single-branch layer, the branch masks of a fixed average, a dropped attention
+    branch - draw masks no model-level test reaches): two layers, loss = <y, fixed random tensor>, central difference along the
+    gradient direction with that test's step (0.2 % of the parameter norm) and its 3e-2 bound (measured on the commit that added
+    the test: 2.7e-5 ... 9.6e-5 over the six forms)."""
+    from oracle.model import fill_parameters_, synth
+    from tavsr import ops
+    from tavsr.encoder.branchformer.encoder import MyBranchformerEncoder
+    from tavsr.layers import RelPositionalEncoding
+    B, T, D = 3, 40, 256
+    enc = MyBranchformerEncoder(input_size=D, output_size=D, attention_heads=4, num_blocks=2, input_layer=None, dropout_rate=0.1,
+                                positional_dropout_rate=0.0, attention_dropout_rate=0.1, ffn_activation_type="swish",
+                                merge_method=merge, cgmlp_weight=cgmlp_weight, attn_branch_drop_rate=branch_drop)
+    fill_parameters_(enc, seed=17)
+    enc = enc.cuda().train()
+    xs, pos = RelPositionalEncoding(D, 0.0)(synth((B, T, D), seed=8).cuda())
+    lens = torch.tensor([40, 27, 20], device="cuda")
+    mask = (torch.arange(T, device="cuda")[None, :] < lens[:, None])[:, None, :]
+    r = synth((B, T, D), seed=10).cuda().double()
+
+    def loss_at():
+        ops.manual_seed(2024)
+        h, m = (xs, pos), mask
+        for layer in enc.encoders:
+            h, m = layer(h, m)
+        return (h[0].double() * r).sum()
+
+    enc.zero_grad()
+    loss_at().backward()
+    params = [p for p in enc.parameters() if p.grad is not None]
+    grads = [p.grad.detach().clone() for p in params]
+    gnorm = float(torch.sqrt(sum((g.double() ** 2).sum() for g in grads)))
+    assert np.isfinite(gnorm) and gnorm > 0
+    eps = 2e-3 / gnorm * float(torch.sqrt(sum((p.double() ** 2).sum() for p in params)))   # ~0.2 % relative step
+    with torch.no_grad():
+        for p, g in zip(params, grads):
+            p.add_(g, alpha=eps / gnorm)
+        lp = float(loss_at())
+        for p, g in zip(params, grads):
+            p.add_(g, alpha=-2 * eps / gnorm)
+        lm = float(loss_at())
+    fd = (lp - lm) / (2 * eps)
+    print(f"frozen-mask layers {merge} {cgmlp_weight} {branch_drop}: fd {fd:.6g} gnorm {gnorm:.6g} rel {abs(fd - gnorm) / gnorm:.3e}")
+    assert abs(fd - gnorm) / gnorm < 3e-2, (fd, gnorm)
+
+
 def test_backward_regenerates_its_own_forward_masks():
     """fwd(A), fwd(B), bwd(A): the second forward advances the device generator, the backward of the first must still
     regenerate the masks ITS forward drew (the dropout tokens own their step's seed) - gradients bit-identical to a lone
