@@ -771,6 +771,23 @@ int tavsr_mask_uniform(const int64_t* text, int64_t ld_text, int32_t B, int32_t 
 int tavsr_count_recip(const int32_t* n, int32_t B, float* inv, tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Language-model training rows (espnet2 lm/espnet_model.py ESPnetLanguageModel.nll, called through lm_main.py:31,54:
+ * x = pad(text, [1, 0], eos), t = pad(text, [0, 1], ignore_id), `for i, l in enumerate(text_lengths): t[i, l] = sos`,
+ * x_lengths = text_lengths + 1).  One workgroup per sentence, one launch, no host value read: capturable.
+ *   For row b of text [B][ld_text] (W columns) with len = clamp(lengths[b], 0, min(W, Wout - 1)):
+ *     x[b][0] = sos_eos, x[b][j] = text[b][j-1] for 1 <= j <= len, 0 for len < j < Wout;
+ *     t[b][j] = text[b][j] for j < len, t[b][len] = sos_eos, -1 for len < j < Wout;
+ *     x_lengths[b] = len + 1 (int64), n[b] = len + 1 (int32, the count tavsr_count_recip takes).
+ *   The rows are delimited by `lengths` alone: the value of text[b][j] for j >= len is never read, so batches padded with -1,
+ *   with 0 or with a valid id give the same outputs.  Wout is the output width (W + 1, or max_length + 1 of nll());
+ *   every element of x and t up to Wout is written.  No width limit.
+ *   lm_row_sums: out[r] = sum_{c < cols} x[r][c] in a fixed order (the per-sentence nll sums of a perplexity).
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_lm_shift(const int64_t* text, int64_t ld_text, const int64_t* lengths, int32_t B, int32_t W, int32_t sos_eos,
+                   int64_t* x, int64_t* t, int64_t ld_y, int32_t Wout, int64_t* x_lengths, int32_t* n, tavsr_stream_t stream);
+int tavsr_lm_row_sums(const float* x, int64_t ldx, float* out, int32_t rows, int32_t cols, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Attention-decoder loss side (espnet LabelSmoothingLoss + th_accuracy, espnet_model.py:553-569)
  * and decoder input embedding (Embedding + PositionalEncoding, espnet transformer_decoder.py).
  *   lsm_loss: row_loss[r] = KL(smoothed one-hot || softmax(logits[r])) (0 for ignored rows),

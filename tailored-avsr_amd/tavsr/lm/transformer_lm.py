@@ -1,8 +1,9 @@
 """``TransformerLM`` - parameter holder with espnet2.lm.transformer_lm.TransformerLM's constructor and state_dict keys
 (configs/LM/lm-english.yaml: pos_enc null, embed 128, att 512, 8 heads, 2048 units, 16 layers), used as the ``lm``
-scorer of the beam search (src/inference/avsr_inference.py:155-170).  Its one-token scoring step runs inside
-``tavsr.inference.beam_search`` on the HIP kernels; ``forward`` (whole sequences, no cache) is the same arithmetic in
-teacher-forced form and exists for checking."""
+scorer of the beam search (src/inference/avsr_inference.py:155-170) and trained through ``tavsr.tasks.lm.ESPnetLanguageModel``
+(lm_main.py:22-57).  Its one-token scoring step runs inside ``tavsr.inference.beam_search`` on the HIP kernels; ``forward``
+(whole sequences, no cache) is the same arithmetic in teacher-forced form: in eval mode without autograd the scoring pass the
+search tests check against, in training mode ``tavsr.functional_lm.TransformerLMFn`` with its hand-written backward."""
 from __future__ import annotations
 
 
@@ -42,19 +43,50 @@ class TransformerLM(torch.nn.Module):
         self.embed = torch.nn.Embedding(vocab_size, embed_unit)
         self.encoder = _Encoder(embed_unit, att_unit, head, unit, layer, dropout_rate)
         self.decoder = torch.nn.Linear(att_unit, vocab_size)
-        self.heads, self.att_unit = head, att_unit
+        self.heads, self.att_unit, self.dropout_rate = head, att_unit, dropout_rate
+
+    def _params(self):
+        cached = self.__dict__.get("_tavsr_pcache")                        # Parameter identities never change: look up once
+        if cached is not None:
+            return cached
+        from ..functional_lm import LM_LAYER_PARAM_NAMES
+        emb = self.encoder.embed
+        P = [self.embed.weight, emb[0].weight, emb[0].bias, emb[1].weight, emb[1].bias]
+        for layer in self.encoder.encoders:
+            named = dict(layer.named_parameters())
+            P += [named[n] for n in LM_LAYER_PARAM_NAMES]
+        P += [self.encoder.after_norm.weight, self.encoder.after_norm.bias, self.decoder.weight, self.decoder.bias]
+        self.__dict__["_tavsr_pcache"] = P
+        return P
+
+    def forward(self, input: torch.Tensor, hidden=None, lengths=None):
+        """input (B, L) int64 -> (logits (B, L, V), None).  ``lengths`` (B) int64: keys of row b from ``lengths[b]`` on are masked
+        (espnet masks keys equal to 0; with the padding at the tail under the causal mask that is the same for every row below
+        ``lengths[b]``, and a 0 inside a sentence is not supported); None: full-length rows with no 0 tokens.
+        In training mode, or when autograd records and a parameter requires a gradient, the pass is ``TransformerLMFn`` (dropout,
+        hand-written backward); otherwise the scoring pass below, unchanged."""
+        P = self._params()
+        if self.training or (torch.is_grad_enabled() and any(p.requires_grad for p in P)):
+            from .. import functional as F_
+            from ..functional_lm import TransformerLMFn
+            B, Lq = input.shape
+            lens = (torch.full((B,), Lq, dtype=torch.int64, device=input.device) if lengths is None
+                    else lengths.to(torch.int64).contiguous())
+            cfg = dict(heads=self.heads, num_blocks=len(self.encoder.encoders))
+            if self.training:
+                cfg["p"] = self.dropout_rate
+            return F_.grad_apply(TransformerLMFn, input.to(torch.int64), lens, cfg, *P), None
+        return self._score_forward(input, lengths)
 
     @torch.no_grad()
-    def forward(self, input: torch.Tensor, hidden=None):
-        """input (B, L) int64 (no 0 tokens: espnet masks keys equal to 0) -> logits (B, L, V); eval only."""
+    def _score_forward(self, input: torch.Tensor, lengths=None):
+        """the eval / no-grad pass (whole sequences, no cache): what the beam-search tests compare the one-token step against"""
         from ..functional import _SelfAttnCore
-        if self.training:
-            raise NotImplementedError("LM training is out of scope (lm_main.py is broken as shipped, SURVEY 2 #14)")
         B, Lq = input.shape
         D, H = self.att_unit, self.heads
         dk = D // H
         M = B * Lq
-        lens = torch.full((B,), Lq, dtype=torch.int64, device=input.device)
+        lens = torch.full((B,), Lq, dtype=torch.int64, device=input.device) if lengths is None else lengths.to(torch.int64)
         e = self.embed.weight[input.reshape(-1)]                     # embedding row gather (index plumbing)
         emb = self.encoder.embed
         h = ops.linear(e.contiguous(), emb[0].weight, emb[0].bias)

@@ -1412,6 +1412,34 @@ def count_recip(n):
     return inv
 
 
+def lm_shift(text, lengths, sos_eos, width=None):
+    """text [B, W] int64, lengths [B] int64 -> (x, t [B, width] int64, x_lengths [B] int64, n [B] int32): the language model's
+    shifted input / target rows built on the device (tavsr_lm_shift; include/tavsr.h has the row layout).  ``width`` defaults to
+    W + 1.  Padded entries of ``text`` are never read as ids: x is 0 and t is -1 behind a sentence whatever ``text`` holds there.
+    No host read, no sync: capturable."""
+    require_cuda(text, lengths)
+    assert text.dim() == 2 and text.dtype == torch.int64 and (text.shape[1] <= 1 or text.stride(1) == 1)
+    assert lengths.dtype == torch.int64 and lengths.is_contiguous() and lengths.shape == (text.shape[0],)
+    B, W = text.shape
+    Wout = W + 1 if width is None else int(width)
+    x = torch.empty((B, Wout), dtype=torch.int64, device=text.device)
+    t = torch.empty((B, Wout), dtype=torch.int64, device=text.device)
+    x_lengths = torch.empty((B,), dtype=torch.int64, device=text.device)
+    n = torch.empty((B,), dtype=torch.int32, device=text.device)
+    check(lib().tavsr_lm_shift(ptr(text), text.stride(0), ptr(lengths), B, W, int(sos_eos), ptr(x), ptr(t), Wout, Wout, ptr(x_lengths),
+                               ptr(n), stream()), "tavsr_lm_shift")
+    return x, t, x_lengths, n
+
+
+def row_sums(x):
+    """x [rows, cols] fp32 -> [rows] sums over the columns in a fixed order (tavsr_lm_row_sums)."""
+    require_cuda(x)
+    assert x.dim() == 2 and x.dtype == f32 and (x.shape[1] <= 1 or x.stride(1) == 1)
+    out = empty(x.shape[0], like=x)
+    check(lib().tavsr_lm_row_sums(ptr(x), x.stride(0), ptr(out), x.shape[0], x.shape[1], stream()), "tavsr_lm_row_sums")
+    return out
+
+
 def lsm_loss(logits2d, target, ignore, smoothing):
     rows, V = logits2d.shape
     require_cuda(logits2d, target)

@@ -300,3 +300,36 @@ def validation(e2e, data_loader, device="cuda"):
             data_loss += float(loss)
             data_cer += float(stats["cer_ctc"]) * 100.0
     return round(data_loss / len(data_loader), 3), round(data_cer / len(data_loader), 3)
+
+
+def lm_training(lm, train_loader, optimizer, scheduler, accum_grad, device="cuda"):
+    """One epoch of language-model training (lm_main.py:22-43).  Batches are tuples (token ids, lengths, ...); the optimizer
+    steps every ``accum_grad`` batches and after the last one, and the loss stays on the device until the epoch ends."""
+    lm.train()
+    total = None
+    optimizer.zero_grad()
+    n = len(train_loader)
+    for batch_idx, batch in enumerate(train_loader):
+        xs_pad, ilens = batch[0].to(device), batch[1].to(device)
+        loss = lm(xs_pad, ilens)[0] / accum_grad
+        loss.backward()
+        if ((batch_idx + 1) % accum_grad == 0) or (batch_idx + 1 == n):
+            optimizer.step()
+            if scheduler is not None:
+                scheduler.step()
+            optimizer.zero_grad()
+        d = loss.detach().reshape(())
+        total = d if total is None else total + d
+    return float(total) / (n / accum_grad)
+
+
+def lm_validation(lm, data_loader, device="cuda"):
+    """lm_main.py:45-57: the mean loss over the loader (the log of the perplexity), rounded to 3 decimals."""
+    lm.eval()
+    data_loss = 0.0
+    with torch.no_grad():
+        for batch in data_loader:
+            xs_pad, ilens = batch[0].to(device), batch[1].to(device)
+            loss, stats, weight = lm(xs_pad, ilens)
+            data_loss += float(loss)
+    return round(data_loss / len(data_loader), 3)
