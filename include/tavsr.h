@@ -718,6 +718,32 @@ int tavsr_ctc_loss(const float* logits, int64_t ld_t, int64_t ld_b, const int64_
 int tavsr_ctc_greedy(const float* logits, int64_t ld_t, int64_t ld_b, const int64_t* hlens, int32_t blank,
                      int64_t* ids, int64_t* hyp, int64_t* hyp_len, int32_t B, int32_t T, int32_t V,
                      tavsr_stream_t stream);
+/* CTC forced alignment: the max-product (Viterbi) pass over the lattice of tavsr_ctc_loss with a back-trace, one workgroup
+ * per alignment problem, one launch, nothing read on the host (capturable).  Problem n aligns target row n (tlens[n] = L
+ * tokens) to row r = rows[n] of the logits (r = n when rows is NULL; an n-best list shares its utterance's logits), over
+ * Tb = min(T, hlens[r]) frames and S = 2L + 1 states; lab(s) = blank at even s, target[n][(s - 1) / 2] at odd s;
+ * lp[t][v] = logits[r][t][v] - logsumexp_v(logits[r][t][:]) in fp32.
+ *   d[0][0] = lp[0][blank], d[0][1] = lp[0][lab(1)], the rest -inf.  For t >= 1 the candidates d[t-1][s] (move 0),
+ *   d[t-1][s-1] (move 1) and, at odd s with lab(s) != lab(s-2), d[t-1][s-2] (move 2) are compared in that order with a
+ *   strict `>`: on a tie the smaller move wins.  d[t][s] = best + lp[t][lab(s)] (-inf stays -inf).  The path ends in state
+ *   S-2 if S >= 2 and d[Tb-1][S-2] > d[Tb-1][S-1], else in S-1; score[n] is that d; the stored moves are walked back.
+ * Outputs, every element written by every call:
+ *   align    [N][T]       int64: lab(path[t]) for t < Tb, -1 for Tb <= t < T
+ *   frame_lp [N][T]       fp32 : lp[t][align[n][t]] for t < Tb, 0 beyond
+ *   span     [N][Lmax][2] int32: first frame in state 2l+1 and the last such frame + 1 for l < L, -1 for L <= l < Lmax
+ *   score    [N]          fp32
+ * Infeasible problems - Tb < L + (number of l with target[l] == target[l-1]), or a label outside [0, V) or equal to blank
+ * (never used as an index) - give score = -inf, align = -1, frame_lp = 0, span = -1 and leave their neighbours alone.
+ * L = 0 is feasible (all blank; score 0 when Tb = 0 too).
+ * The moves take 2 bits per (frame, state): T * ceil((2 Lmax + 1) / 16) words.  ws == NULL keeps them in the workgroup's LDS
+ * (TAVSR_EUNSUPPORTED when tavsr_ctc_align_lds_ok(T, Lmax) is 0); ws != NULL (>= tavsr_ctc_align_ws(N, T, Lmax) bytes,
+ * 4-byte aligned) keeps them there at any size.  One kernel body runs both routes: their results are bit-identical. */
+int tavsr_ctc_align_lds_ok(int32_t T, int32_t Lmax);
+int64_t tavsr_ctc_align_ws(int32_t N, int32_t T, int32_t Lmax);
+int tavsr_ctc_align(const float* logits, int64_t ld_t, int64_t ld_b, const int64_t* hlens, const int32_t* rows,
+                    const int64_t* targets, int64_t ld_tgt, const int64_t* tlens, int32_t blank, int64_t* align,
+                    float* frame_lp, int32_t* span, float* score, void* ws, int32_t N, int32_t T, int32_t V, int32_t Lmax,
+                    tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Mask-CTC decoding (src/models/maskctc_model.py:285-349, MaskCTCInference.forward), one workgroup per utterance,

@@ -2,6 +2,7 @@
 // src/ctc/ctc.py:58-69,143-156) and greedy decode (argmax at ctc.py:180-188 + the collapse at
 // src/models/maskctc_model.py:289-291).  One workgroup per utterance; the alpha lattice lives in a
 // caller-provided workspace, the beta recursion is fused with the gradient.  Log-space fp32.
+// Forced alignment (tavsr_ctc_align): the max-product pass over the same lattice with a back-trace, one workgroup per problem.
 #include <float.h>
 #include <math.h>
 
@@ -268,6 +269,238 @@ __global__ __launch_bounds__(256) void ctc_greedy_kernel(const float* __restrict
   }
 }
 
+// ---- forced alignment: the max-product pass over the same lattice, with a back-trace (contract: include/tavsr.h).
+// One workgroup per problem.  LDS, in 4-byte words: d[2][Smax] | label + skip bit [Smax] | lz[T] | path[T] | emissions
+// [kAlignChunk][Smax] | 8 words of reduction scratch | (LDS route) the moves [T][W], W = ceil(Smax / 16).  The emissions
+// lp[t][lab(s)] of kAlignChunk frames are gathered from HBM by all threads, then that chunk's dependent steps run out of LDS:
+// a step is three LDS reads, two compares, the row-of-16 OR below, two LDS writes and one barrier, and never a global load.
+// Moves: 2 bits per state; the 16 lanes of a DPP row hold the 16 states of one word, OR their shifted moves over the row
+// (four lane-network steps) and the row's first lane stores the whole word - no atomics, no read-modify-write.
+constexpr int kAlignChunk = 16;
+constexpr int kAlignLdsBytes = 160 * 1024;
+constexpr uint32_t kSkipBit = 0x80000000u;
+
+struct AlignLds { int64_t d, lab, lz, path, em, red, moves, words; };
+__host__ __device__ inline AlignLds align_lds(int T, int Smax, bool moves_in_lds) {
+  AlignLds o;
+  o.d = 0;
+  o.lab = o.d + 2 * (int64_t)Smax;
+  o.lz = o.lab + Smax;
+  o.path = o.lz + T;
+  o.em = o.path + T;
+  o.red = o.em + (int64_t)kAlignChunk * Smax;
+  o.moves = o.red + 8;
+  o.words = o.moves + (moves_in_lds ? (int64_t)T * ((Smax + 15) / 16) : 0);
+  return o;
+}
+
+// OR over each row of 16 lanes (every lane of the row gets it); all 64 lanes must be active
+__device__ __forceinline__ uint32_t row16_or(uint32_t v) {
+  TAVSR_ASSERT_FULL_WAVE();
+#define TAVSR_DPP_OR(CTRL) v |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false)
+  TAVSR_DPP_OR(0xB1);       // quad_perm [1, 0, 3, 2]
+  TAVSR_DPP_OR(0x4E);       // quad_perm [2, 3, 0, 1]
+  TAVSR_DPP_OR(0x141);      // row_half_mirror
+  TAVSR_DPP_OR(0x140);      // row_mirror
+#undef TAVSR_DPP_OR
+  return v;
+}
+
+// `moves`: [T][W] words, in LDS or in the caller's workspace; kStage (workspace route): the back-trace reads them through LDS,
+// a block of rows at a time, instead of walking a chain of dependent HBM loads.  Everything else is one code path.
+template <bool kStage>
+__device__ __forceinline__ void ctc_align_body(const float* __restrict__ logits, int64_t ld_t, int64_t ld_b,
+                                               const int64_t* __restrict__ hlens, const int32_t* __restrict__ rows,
+                                               const int64_t* __restrict__ targets, int64_t ld_tgt,
+                                               const int64_t* __restrict__ tlens, int blank, int64_t* __restrict__ align,
+                                               float* __restrict__ frame_lp, int32_t* __restrict__ span,
+                                               float* __restrict__ score, uint32_t* moves, float* sm, int T, int V, int Lmax) {
+  const int Smax = 2 * Lmax + 1, W = (Smax + 15) / 16;
+  const AlignLds o = align_lds(T, Smax, false);
+  float* s_d = sm + o.d;
+  uint32_t* s_lab = reinterpret_cast<uint32_t*>(sm + o.lab);
+  float* s_lz = sm + o.lz;
+  int* s_path = reinterpret_cast<int*>(sm + o.path);
+  float* s_em = sm + o.em;
+  int* s_red = reinterpret_cast<int*>(sm + o.red);
+  const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t r = rows ? rows[n] : n;
+  const int64_t hl = hlens[r];
+  const int Tb = (int)(hl < 0 ? 0 : (hl < T ? hl : T));
+  const int64_t tl = tlens[n];
+  const bool len_ok = tl >= 0 && tl <= Lmax;
+  const int L = len_ok ? (int)tl : 0;
+  const int S = 2 * L + 1;
+  const int64_t* tgt = targets + (int64_t)n * ld_tgt;
+  const float* lg = logits + r * ld_b;
+  int64_t* al = align + (int64_t)n * T;
+  float* fl = frame_lp + (int64_t)n * T;
+  int32_t* sp = span + (int64_t)n * Lmax * 2;
+
+  // feasibility: every label inside [0, V) and not blank, and Tb >= L + repeats.  A label that fails is never an index.
+  int bad = 0, rep = 0;
+  for (int l = tid; l < L; l += 256) {
+    const int64_t c = tgt[l];
+    bad |= (c < 0 || c >= V || c == blank);
+    rep += (l >= 1 && c == tgt[l - 1]);
+  }
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) {
+    bad |= __shfl_xor(bad, m, 64);
+    rep += __shfl_xor(rep, m, 64);
+  }
+  if (lane == 0) { s_red[wv] = bad; s_red[4 + wv] = rep; }
+  __syncthreads();
+  bad = s_red[0] | s_red[1] | s_red[2] | s_red[3];
+  rep = s_red[4] + s_red[5] + s_red[6] + s_red[7];
+  const bool feasible = len_ok && !bad && Tb >= L + rep;
+
+  for (int i = tid; i < 2 * Lmax; i += 256) sp[i] = -1;
+  if (!feasible) {
+    for (int t = tid; t < T; t += 256) { al[t] = -1; fl[t] = 0.f; }
+    if (tid == 0) score[n] = -INFINITY;
+    return;
+  }
+
+  for (int s = tid; s < S; s += 256) {
+    uint32_t lab = (uint32_t)blank;
+    if (s & 1) {
+      lab = (uint32_t)tgt[s >> 1];
+      if (s >= 3 && tgt[s >> 1] != tgt[(s >> 1) - 1]) lab |= kSkipBit;
+    }
+    s_lab[s] = lab;
+  }
+  for (int t = wv; t < Tb; t += 4) {
+    const float* row = lg + (int64_t)t * ld_t;
+    float mx = -FLT_MAX;      // (unrolled: eight loads in flight per lane, the sums still in index order - a row of V = 5000 is 79 trips)
+#pragma unroll 8
+    for (int v = lane; v < V; v += 64) mx = fmaxf(mx, row[v]);
+    mx = wave_max(mx);
+    float se = 0.f;
+#pragma unroll 8
+    for (int v = lane; v < V; v += 64) se += expf(row[v] - mx);
+    se = wave_sum(se);
+    if (lane == 0) s_lz[t] = mx + logf(se);
+  }
+  __syncthreads();
+
+  float* dp = s_d;             // d[t-1]
+  float* dc = s_d + Smax;      // d[t]
+  for (int t0 = 0; t0 < Tb; t0 += kAlignChunk) {
+    const int nc = min(kAlignChunk, Tb - t0);
+    for (int i = tid; i < nc * S; i += 256) {
+      const int c = i / S, s = i - c * S, t = t0 + c;
+      s_em[c * Smax + s] = lg[(int64_t)t * ld_t + (s_lab[s] & ~kSkipBit)] - s_lz[t];
+    }
+    __syncthreads();
+    for (int c = 0; c < nc; ++c) {
+      const int t = t0 + c;
+      const float* em = s_em + c * Smax;
+      if (t == 0) {
+        for (int s = tid; s < S; s += 256) dc[s] = s < 2 ? em[s] : -INFINITY;
+      } else {
+        for (int base = 0; base < S; base += 256) {      // uniform: row16_or needs whole waves
+          const int s = base + tid;
+          uint32_t mv = 0;
+          if (s < S) {
+            float best = dp[s];
+            if (s >= 1) {
+              const float a1 = dp[s - 1];
+              if (a1 > best) { best = a1; mv = 1; }
+            }
+            if (s >= 2 && (s_lab[s] & kSkipBit)) {
+              const float a2 = dp[s - 2];
+              if (a2 > best) { best = a2; mv = 2; }
+            }
+            dc[s] = best == -INFINITY ? -INFINITY : best + em[s];
+          }
+          const uint32_t word = row16_or(mv << (2 * (tid & 15)));
+          if ((tid & 15) == 0 && s < S) moves[(int64_t)t * W + (s >> 4)] = word;
+        }
+      }
+      __syncthreads();
+      float* tmp = dp; dp = dc; dc = tmp;
+    }
+  }
+
+  // ---- back-trace (one thread; path[] in LDS), then the outputs in parallel
+  int s_end = 0;
+  if (Tb > 0) s_end = (S >= 2 && dp[S - 2] > dp[S - 1]) ? S - 2 : S - 1;
+  if (tid == 0) {
+    score[n] = Tb > 0 ? dp[s_end] : 0.f;
+    if (Tb > 0) s_path[Tb - 1] = s_end;
+  }
+  if (!kStage) {
+    if (tid == 0) {
+      int s = s_end;
+      for (int t = Tb - 1; t >= 1; --t) {
+        s -= (int)((moves[(int64_t)t * W + (s >> 4)] >> (2 * (s & 15))) & 3u);
+        s_path[t - 1] = s;
+      }
+    }
+  } else {
+    // rows [t_lo, t_hi] of the move table through the emission buffer (kAlignChunk * Smax >= 16 W words: >= 16 rows)
+    uint32_t* s_mv = reinterpret_cast<uint32_t*>(s_em);
+    const int R = (kAlignChunk * Smax) / W;
+    int s = s_end;
+    for (int t_hi = Tb - 1; t_hi >= 1; t_hi -= R) {
+      const int t_lo = max(1, t_hi - R + 1), cnt = (t_hi - t_lo + 1) * W;
+      for (int i = tid; i < cnt; i += 256) s_mv[i] = moves[(int64_t)t_lo * W + i];
+      __syncthreads();
+      if (tid == 0) {
+        for (int t = t_hi; t >= t_lo; --t) {
+          s -= (int)((s_mv[(t - t_lo) * W + (s >> 4)] >> (2 * (s & 15))) & 3u);
+          s_path[t - 1] = s;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  __syncthreads();
+  for (int t = tid; t < T; t += 256) {
+    int64_t a = -1;
+    float f = 0.f;
+    if (t < Tb) {
+      const int s = s_path[t];
+      const int lab = (int)(s_lab[s] & ~kSkipBit);
+      a = lab;
+      f = lg[(int64_t)t * ld_t + lab] - s_lz[t];
+      if (s & 1) {      // a state's frames are one run: each end is found by exactly one thread
+        if (t == 0 || s_path[t - 1] != s) sp[2 * (s >> 1)] = t;
+        if (t == Tb - 1 || s_path[t + 1] != s) sp[2 * (s >> 1) + 1] = t + 1;
+      }
+    }
+    al[t] = a;
+    fl[t] = f;
+  }
+}
+
+__global__ __launch_bounds__(256) void ctc_align_lds_kernel(const float* __restrict__ logits, int64_t ld_t, int64_t ld_b,
+                                                            const int64_t* __restrict__ hlens, const int32_t* __restrict__ rows,
+                                                            const int64_t* __restrict__ targets, int64_t ld_tgt,
+                                                            const int64_t* __restrict__ tlens, int blank,
+                                                            int64_t* __restrict__ align, float* __restrict__ frame_lp,
+                                                            int32_t* __restrict__ span, float* __restrict__ score, int T, int V,
+                                                            int Lmax) {
+  extern __shared__ float sm[];
+  uint32_t* moves = reinterpret_cast<uint32_t*>(sm + align_lds(T, 2 * Lmax + 1, true).moves);
+  ctc_align_body<false>(logits, ld_t, ld_b, hlens, rows, targets, ld_tgt, tlens, blank, align, frame_lp, span, score, moves, sm,
+                        T, V, Lmax);
+}
+
+__global__ __launch_bounds__(256) void ctc_align_ws_kernel(const float* __restrict__ logits, int64_t ld_t, int64_t ld_b,
+                                                           const int64_t* __restrict__ hlens, const int32_t* __restrict__ rows,
+                                                           const int64_t* __restrict__ targets, int64_t ld_tgt,
+                                                           const int64_t* __restrict__ tlens, int blank,
+                                                           int64_t* __restrict__ align, float* __restrict__ frame_lp,
+                                                           int32_t* __restrict__ span, float* __restrict__ score,
+                                                           uint32_t* __restrict__ ws, int T, int V, int Lmax) {
+  extern __shared__ float sm[];
+  uint32_t* moves = ws + (int64_t)blockIdx.x * T * ((2 * Lmax + 1 + 15) / 16);
+  ctc_align_body<true>(logits, ld_t, ld_b, hlens, rows, targets, ld_tgt, tlens, blank, align, frame_lp, span, score, moves, sm, T,
+                       V, Lmax);
+}
+
 // Label-smoothing KL loss (espnet LabelSmoothingLoss, espnet_model.py:175-180,563) fused with its
 // gradient and the th_accuracy counters.  One wave per (b, l) row.
 __global__ __launch_bounds__(256) void lsm_loss_kernel(const float* __restrict__ logits, int64_t ld,
@@ -413,6 +646,53 @@ extern "C" int tavsr_ctc_greedy(const float* logits, int64_t ld_t, int64_t ld_b,
   if (B <= 0 || T <= 0) return TAVSR_OK;
   hipLaunchKernelGGL(ctc_greedy_kernel, dim3(B), dim3(256), 0, (hipStream_t)stream, logits, ld_t, ld_b, hlens, blank, ids,
                      hyp, hyp_len, T, V);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
+static bool ctc_align_sizes_ok(int64_t T, int64_t Lmax) { return T >= 0 && Lmax >= 0 && T <= (1 << 24) && Lmax <= (1 << 24); }
+
+extern "C" int tavsr_ctc_align_lds_ok(int32_t T, int32_t Lmax) {
+  if (!ctc_align_sizes_ok(T, Lmax)) return 0;
+  return align_lds(T, 2 * Lmax + 1, true).words * 4 <= kAlignLdsBytes;
+}
+
+extern "C" int64_t tavsr_ctc_align_ws(int32_t N, int32_t T, int32_t Lmax) {
+  if (N <= 0 || !ctc_align_sizes_ok(T, Lmax)) return 0;
+  return (int64_t)N * T * ((2 * (int64_t)Lmax + 1 + 15) / 16) * 4;
+}
+
+extern "C" int tavsr_ctc_align(const float* logits, int64_t ld_t, int64_t ld_b, const int64_t* hlens, const int32_t* rows,
+                               const int64_t* targets, int64_t ld_tgt, const int64_t* tlens, int32_t blank, int64_t* align,
+                               float* frame_lp, int32_t* span, float* score, void* ws, int32_t N, int32_t T, int32_t V,
+                               int32_t Lmax, tavsr_stream_t stream) {
+  if (N <= 0) return TAVSR_OK;
+  TAVSR_REQUIRE(hlens && tlens && score && (T == 0 || (logits && align && frame_lp)) && (Lmax == 0 || (targets && span)),
+                TAVSR_EINVAL, "ctc_align: null pointer");
+  TAVSR_REQUIRE(ctc_align_sizes_ok(T, Lmax) && V > 0 && blank >= 0 && blank < V && ld_t >= V && ld_tgt >= Lmax, TAVSR_EINVAL,
+                "ctc_align: bad sizes (T=%d V=%d Lmax=%d blank=%d ld_t=%lld ld_tgt=%lld)", T, V, Lmax, blank, (long long)ld_t,
+                (long long)ld_tgt);
+  TAVSR_REQUIRE(((uintptr_t)ws & 3) == 0, TAVSR_EINVAL, "ctc_align: the workspace must be 4-byte aligned");
+  const int Smax = 2 * Lmax + 1;
+  const int64_t bytes = align_lds(T, Smax, ws == nullptr).words * 4;
+  if (!ws)
+    TAVSR_REQUIRE(bytes <= kAlignLdsBytes, TAVSR_EUNSUPPORTED,
+                  "ctc_align: the move table of T=%d, Lmax=%d does not fit a workgroup's LDS (tavsr_ctc_align_lds_ok): pass a "
+                  "workspace of tavsr_ctc_align_ws bytes", T, Lmax);
+  else
+    TAVSR_REQUIRE(bytes <= kAlignLdsBytes, TAVSR_EUNSUPPORTED, "ctc_align: T=%d / Lmax=%d exceed the LDS budget of the lattice rows",
+                  T, Lmax);
+  const void* fn = ws ? reinterpret_cast<const void*>(ctc_align_ws_kernel) : reinterpret_cast<const void*>(ctc_align_lds_kernel);
+  if (bytes > 48 * 1024) {      // the > 64 KB dynamic-LDS opt-in, as tavsr_ctc_loss
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kAlignLdsBytes);
+    TAVSR_REQUIRE(e == hipSuccess, TAVSR_EUNSUPPORTED, "ctc_align: hipFuncSetAttribute: %s", hipGetErrorString(e));
+  }
+  if (ws)
+    hipLaunchKernelGGL(ctc_align_ws_kernel, dim3((unsigned)N), dim3(256), (size_t)bytes, (hipStream_t)stream, logits, ld_t, ld_b, hlens,
+                       rows, targets, ld_tgt, tlens, blank, align, frame_lp, span, score, (uint32_t*)ws, T, V, Lmax);
+  else
+    hipLaunchKernelGGL(ctc_align_lds_kernel, dim3((unsigned)N), dim3(256), (size_t)bytes, (hipStream_t)stream, logits, ld_t, ld_b, hlens,
+                       rows, targets, ld_tgt, tlens, blank, align, frame_lp, span, score, T, V, Lmax);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
 }

@@ -50,6 +50,15 @@ class CTC(torch.nn.Module):
         with torch.no_grad():
             return ops.ctc_greedy(self._logits(hs_pad), hlens.to(torch.int64), blank, collapse=True)
 
+    def forced_align(self, hs_pad, hlens, ys_pad, ys_lens, blank: int = 0, rows=None):
+        """Viterbi alignment of the token rows ``ys_pad`` (N, Lmax; any padding beyond ``ys_lens``) to the head's frames:
+        (align (N,T) int64, frame_lp (N,T), span (N,Lmax,2) int32, score (N)) as ``ops.ctc_align`` defines them.  ``rows``
+        (int32, N): the utterance of every token row (an n-best list); None: row n aligns to utterance n.  Inference: no
+        gradient, and no dropout - ``forward``'s always-on dropout is a quirk of the loss, not of the head."""
+        with torch.no_grad():
+            return ops.ctc_align(self._logits(hs_pad), hlens.to(torch.int64).contiguous(), ys_pad.to(torch.int64).contiguous(),
+                                 ys_lens.to(torch.int64).contiguous(), blank, rows=rows)
+
     def softmax(self, hs_pad):
         """(B,Tmax,eprojs) -> frame posteriors (B,Tmax,odim)  (src/ctc/ctc.py:160-168).  Forward only: the differentiable
         use of the posteriors (self-conditioned intermediate CTC) is ``functional.InterCTCConditionFn``."""

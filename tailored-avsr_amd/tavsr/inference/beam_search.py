@@ -31,6 +31,7 @@ from typing import Optional
 import torch
 
 from .. import ops
+from ..utils.timestamps import timestamp_record
 from .search_host import D_END, HostSearch
 
 EPS = 1e-12
@@ -784,7 +785,15 @@ class Speech2Text:
 
     def __init__(self, asr_model, lm=None, beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
                  penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0,
-                 skip_zero_weight: bool = False):
+                 skip_zero_weight: bool = False, timestamps: bool = False, frame_seconds: float = 0.04):
+        # timestamps: every returned hypothesis is aligned to its utterance's CTC posteriors after the search (one launch of
+        # tavsr_ctc_align for the whole batch) and its result tuple gains a fifth element, the record of utils/timestamps.py.
+        # frame_seconds: one encoder frame - 10 ms hop x 4 subsampling for audio, 25 fps for video: 0.04 s in every shipped recipe.
+        if timestamps and asr_model.ctc is None:
+            raise ValueError("timestamps need the CTC head: this model was built without one (ctc_weight: 0.0)")
+        if timestamps and not frame_seconds > 0.0:
+            raise ValueError(f"frame_seconds must be positive: {frame_seconds}")
+        self.timestamps, self.frame_seconds = bool(timestamps), float(frame_seconds)
         self.asr_model = asr_model.eval()
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
@@ -810,4 +819,28 @@ class Speech2Text:
                 text = "".join(token).replace("<space>", " ")
                 res.append((text, token, token_int, (ys, sc)))
             results.append(res)
-        return results
+        return self._with_timestamps(results, enc, enc_lens) if self.timestamps else results
+
+    def _with_timestamps(self, results, enc, enc_lens):
+        """align every hypothesis of every utterance in one launch (``rows``: hypothesis -> utterance), read the alignments back
+        in one copy and append the timestamp record (None for a hypothesis CTC cannot emit) to every result tuple"""
+        flat = [(u, r) for u, res in enumerate(results) for r in res]
+        if not flat:
+            return results
+        N, Lmax = len(flat), max(len(r[2]) for _, r in flat)
+        ys = torch.zeros((N, Lmax), dtype=torch.int64)
+        for n, (_, r) in enumerate(flat):
+            ys[n, : len(r[2])] = torch.tensor(r[2], dtype=torch.int64)
+        dev = enc.device
+        ys_lens = torch.tensor([len(r[2]) for _, r in flat], dtype=torch.int64).to(dev)
+        rows = torch.tensor([u for u, _ in flat], dtype=torch.int32).to(dev)
+        _, frame_lp, span, score = self.asr_model.ctc.forced_align(enc.contiguous().float(), enc_lens.to(dev), ys.to(dev), ys_lens,
+                                                                   self.asr_model.blank_id, rows=rows)
+        T = frame_lp.shape[1]
+        packed = torch.cat([frame_lp, score.view(N, 1), span.view(N, 2 * Lmax).view(torch.float32)], dim=1).cpu()
+        frame_lp, score = packed[:, :T].tolist(), packed[:, T].tolist()
+        span = packed[:, T + 1:].contiguous().view(torch.int32).view(N, Lmax, 2).tolist()
+        out = [[] for _ in results]
+        for n, (u, r) in enumerate(flat):
+            out[u].append(r + (timestamp_record(r[1], span[n], frame_lp[n], score[n], self.frame_seconds),))
+        return out

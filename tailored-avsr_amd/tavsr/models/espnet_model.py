@@ -267,6 +267,19 @@ class ESPnetASRModel(torch.nn.Module):
         enc, olens = self.encode(speech, speech_lengths)
         return self.ctc.greedy(enc, olens, self.blank_id)
 
+    @torch.no_grad()
+    def align(self, *batch):
+        """(*encode's tensors, text, text_lengths) -> (align (B,T) int64, frame_lp (B,T), span (B,Lmax,2) int32, score (B),
+        encoder_out_lens): the CTC forced alignment of every utterance to its transcript (``CTC.forced_align``; frames are the
+        encoder's).  ``text`` (B,Lmax) is read up to ``text_lengths``; its padding may hold anything."""
+        *inputs, text, text_lengths = batch
+        if self.ctc is None:
+            raise ValueError("align needs the CTC head: this model was built without one (ctc_weight: 0.0)")
+        enc, olens = self.encode(*inputs)
+        if isinstance(enc, tuple):
+            enc = enc[0]
+        return self.ctc.forced_align(enc, olens, text, text_lengths, self.blank_id) + (olens,)
+
 
 class _Accuracy:
     """Lazy th_accuracy: the reference returns a Python float (a device->host sync, nets_utils.th_accuracy);

@@ -1355,6 +1355,48 @@ def ctc_greedy(logits, hlens=None, blank=0, collapse=True):
     return ids, hyp, hl
 
 
+CTC_ALIGN_CHUNK = 16      # frames of emissions the alignment kernel gathers into LDS at a time (kAlignChunk, csrc/ctc.hip)
+
+
+def ctc_align_lds_ok(T, Lmax) -> bool:
+    """does the move table of (frames, longest target) fit a workgroup's LDS?  the library's answer (tavsr_ctc_align_lds_ok)"""
+    return bool(lib().tavsr_ctc_align_lds_ok(int(T), int(Lmax)))
+
+
+def ctc_align(logits, hlens, targets, tlens, blank=0, rows=None, route=None):
+    """CTC forced alignment (tavsr_ctc_align: Viterbi over the CTC lattice with a back-trace, one launch, nothing read on the
+    host).  logits [B, T, >= V] fp32 - a view whose row stride exceeds V (4-padded rows) is taken as it is; hlens int64 [B];
+    targets int64 [N, Lmax] (any padding), tlens int64 [N]; rows int32 [N] (or None: N == B, problem n uses logits row n) names
+    the logits row of every problem.  -> (align int64 [N, T], frame_lp fp32 [N, T], span int32 [N, Lmax, 2], score fp32 [N]);
+    an infeasible problem has score -inf, align -1, frame_lp 0 and span -1.  ``route``: None (LDS when the move table fits,
+    else the workspace), "lds" or "ws"."""
+    B, T, V = logits.shape
+    N, Lmax = targets.shape
+    require_cuda(logits, hlens, targets, tlens, rows)
+    assert logits.dtype == f32 and logits.stride(2) == 1 and logits.stride(1) >= V and (B <= 1 or logits.stride(0) >= T * logits.stride(1))
+    assert hlens.dtype == torch.int64 and hlens.numel() == B and hlens.is_contiguous()
+    assert tlens.dtype == torch.int64 and tlens.numel() == N and tlens.is_contiguous()
+    assert targets.dtype == torch.int64 and (Lmax == 0 or targets.stride(1) == 1) and (N <= 1 or targets.stride(0) >= Lmax)
+    if rows is None:
+        assert N == B, "ctc_align: without rows every logits row is one problem"
+    else:
+        assert rows.dtype == torch.int32 and rows.numel() == N and rows.is_contiguous()
+    if route not in (None, "lds", "ws"):
+        raise ValueError(f"ctc_align: route must be None, 'lds' or 'ws': {route!r}")
+    if route is None:
+        route = "lds" if ctc_align_lds_ok(T, Lmax) else "ws"
+    dev = logits.device
+    align = torch.empty((N, T), dtype=torch.int64, device=dev)
+    frame_lp = empty(N, T, like=logits)
+    span = torch.empty((N, Lmax, 2), dtype=torch.int32, device=dev)
+    score = empty(N, like=logits)
+    ws = torch.empty((max(lib().tavsr_ctc_align_ws(N, T, Lmax), 4),), dtype=torch.uint8, device=dev) if route == "ws" else None
+    check(lib().tavsr_ctc_align(ptr(logits), logits.stride(1), logits.stride(0), ptr(hlens), ptr(rows), ptr(targets),
+                                max(targets.stride(0), Lmax), ptr(tlens), int(blank), ptr(align), ptr(frame_lp), ptr(span),
+                                ptr(score), ptr(ws), N, T, V, Lmax, stream()), "tavsr_ctc_align")
+    return align, frame_lp, span, score
+
+
 def maskctc_init(logits, hlens, blank, mask_token, threshold, n_iterations):
     """CTC logits [B,T,V] -> (y_in, y_hat [B,max(T,1)] int64, tok_prob [B,max(T,1)], y_len [B] int64,
     plan [B,3] int32 = (mask_num, num_iter, per_iter)): the start of MaskCTCInference.forward (tavsr_maskctc_init)."""
