@@ -1056,6 +1056,28 @@ int tavsr_ctc_beam_search_ok(int32_t K, int32_t V, int32_t T);
 int tavsr_ctc_beam_search(const float* logp, const int64_t* lens, const int32_t* maxlen, int32_t* hist, int32_t* n_steps, int32_t U,
                           int32_t K, int32_t T, int32_t V, int32_t hist_steps, int32_t sos, int32_t eos, int32_t blank, float w_ctc,
                           float add, int32_t end_detect, float d_end, tavsr_stream_t stream);
+/* N-gram LM scorer of the beam search (the reference's `ngram` scorer: src/inference/avsr_inference.py:166-178 builds espnet's
+ * NgramFullScorer / NgramPartScorer over a KenLM model; here: ARPA tables in device memory, tavsr/lm/ngram.py:NgramLM builds them).
+ * Tables - a forward trie in CSR form over ONE numbering of all n-grams: nodes 0 .. n_unigrams - 1 are the unigrams (node = word id),
+ * then the bigrams, ... ; the k-gram (w1 .. wk) is the child `wk` of the node of (w1 .. wk-1).
+ *   word [n_nodes] int32: last word of the node's n-gram; ascending inside a parent's child range
+ *   logp / backoff [n_nodes] fp32: the file's log10 values (backoff 0 where the file has none)
+ *   child_begin [n_nodes + 1] int32: the children of node i are nodes child_begin[i] .. child_begin[i + 1] - 1
+ *   word_map [V] int32: token id -> word id, -1 for a token without word (scores unk_logp at the unigram level, is listed nowhere)
+ * Hypothesis n is yseq[n][0 .. i] (row stride ld_y, L columns; i = *step_dev when step_dev is given - a captured step - else `step`,
+ * clamped to [0, L - 1]).  Its context is the word sequence <s> = bos_word (-1: the file has no <s>) for position 0, whatever token
+ * stands there, and word_map[yseq[n][p]] for 0 < p <= i, cut to its last order - 1 words.  score(n, v) is standard backoff, from the
+ * longest context suffix to the empty one: the log10 p of (suffix, word(v)) where that n-gram is listed, plus the backoffs of the
+ * longer suffixes that were listed themselves (a suffix that is not listed adds 0); the unigram level always ends the chain.
+ *   out[n][v] = (accumulate ? out[n][v] : 0) + alpha * score(n, v) + add        for every v < V,
+ * or, with cand [N][C] int64 given, for the tokens v = cand[n][c] alone (distinct per row; the rest of the row is left as it is).
+ * One workgroup per hypothesis, one launch, no host read, no allocation.  order <= TAVSR_NGRAM_MAX_ORDER, else TAVSR_EUNSUPPORTED;
+ * a null table: TAVSR_EINVAL.  Call site: ops.ngram_score, BatchBeamSearch._device_step. */
+enum { TAVSR_NGRAM_MAX_ORDER = 8 };
+int tavsr_ngram_score(const int32_t* word, const float* logp, const float* backoff, const int32_t* child_begin, int32_t n_unigrams,
+                      int32_t order, int32_t bos_word, float unk_logp, const int32_t* word_map, const int64_t* yseq, int64_t ld_y,
+                      int32_t L, int32_t step, const int32_t* step_dev, const int64_t* cand, int32_t C, float alpha, float add,
+                      int32_t accumulate, float* out, int64_t ldo, int32_t N, int32_t V, tavsr_stream_t stream);
 /* y = act(x) elementwise (the LM's Linear -> LayerNorm -> ReLU input layer); in place allowed */
 int tavsr_act_fwd(const float* x, float* y, int64_t n, int32_t act, tavsr_stream_t stream);
 

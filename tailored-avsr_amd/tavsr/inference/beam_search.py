@@ -14,6 +14,8 @@ advance together (the reference decodes one utterance at a time on the CPU):
 * The per-step bookkeeping is index plumbing on [N]-sized tensors: top-k and ancestor-list gathers in the beam-update launches,
   ended-hypothesis lists and end detection on the host (inference/search_host.py).
 
+* An n-gram LM (``ngram=``, tavsr/lm/ngram.py: an ARPA file as tables in device memory) is the fifth scorer: one launch per token
+  (``tavsr_ngram_score``) adds its weighted log10 scores to the full scorers' row ("full") or to the pre-beam's candidates ("part").
 * The scorer set is espnet's: a scorer that is None or has weight 0 drops out (a model without decoder: CTC prefix beam search, with
   or without LM; a model without CTC head: attention beam search).  Scorers {ctc, length_bonus} without pre-beam are searched in ONE
   launch per batch (``tavsr_ctc_beam_search``: the beam's lattice stays in LDS), the host replaying its bookkeeping over the records.
@@ -316,7 +318,8 @@ class _LMStep:
 
 class BatchBeamSearch:
     def __init__(self, model, lm=None, beam_size: int = 10, ctc_weight: float = 0.1, lm_weight: float = 0.6,
-                 penalty: float = 0.5, maxlenratio: float = 0.0, minlenratio: float = 0.0, skip_zero_weight: bool = False):
+                 penalty: float = 0.5, maxlenratio: float = 0.0, minlenratio: float = 0.0, skip_zero_weight: bool = False,
+                 ngram=None, ngram_weight: float = 0.9, ngram_scorer: str = "full"):
         if not (0.0 <= ctc_weight <= 1.0):
             raise ValueError(f"ctc_weight must lie in [0, 1]: {ctc_weight}")
         # The scorer set is espnet's (BeamSearch.__init__ drops a scorer that is None or has weight 0; avsr_inference.py:141-153):
@@ -328,6 +331,15 @@ class BatchBeamSearch:
         self.has_dec = model.decoder is not None and not (drop and 1.0 - ctc_weight == 0.0)
         self.has_ctc = model.ctc is not None and not (drop and ctc_weight == 0.0)
         self.has_lm = lm is not None and lm_weight != 0.0
+        # the n-gram scorer (tavsr/lm/ngram.py:NgramLM; avsr_inference.py:166-178): "full" - its weighted row joins the full scorers' row
+        # in front of the pre-beam; "part" - it is added to the pre-beam's candidates only, behind the pre-beam (espnet's partial scorers
+        # score part_ids alone).  None or weight 0 drops it, as every scorer.
+        if ngram_scorer not in ("full", "part"):
+            raise ValueError(f"ngram_scorer must be 'full' or 'part': {ngram_scorer!r}")
+        self.ngram, self.w_ngram, self.ngram_scorer = ngram, float(ngram_weight), ngram_scorer
+        if ngram is not None and ngram.word_map.numel() != len(model.token_list):
+            raise ValueError(f"the n-gram's word map has {ngram.word_map.numel()} tokens, the model's token list {len(model.token_list)}: "
+                             "build it with NgramLM.from_arpa(path, model.token_list, device)")
         if not self.has_dec and not self.has_ctc:
             raise ValueError(f"no scorer is left to search with: the model has {'no' if model.decoder is None else 'a'} decoder and "
                              f"{'no' if model.ctc is None else 'a'} CTC head, and ctc_weight = {ctc_weight} gives the one it has weight 0. "
@@ -346,10 +358,10 @@ class BatchBeamSearch:
         self.C = self.V if ctc_weight == 1.0 else min(int(1.5 * beam_size), self.V)
         # espnet's do_pre_beam: a partial scorer is present, ctc_weight != 1 (pre_beam_score_key = None there) and fewer candidates than tokens
         self.pre_beam = self.has_ctc and ctc_weight != 1.0 and int(1.5 * beam_size) < self.V
-        if self.pre_beam and not self.has_dec and not self.has_lm:
+        if self.pre_beam and not self.has_dec and not self.has_lm and not (self.has_ngram and not self._ngram_part):
             raise ValueError(f"ctc_weight = {ctc_weight} on a model without decoder and without LM: the pre-beam of the CTC prefix scorer "
                              "would rank the length bonus alone, a constant - which candidates it keeps is not defined.  Set "
-                             "ctc_weight: 1.0 (CTC prefix beam search over every token), or add an LM")
+                             "ctc_weight: 1.0 (CTC prefix beam search over every token), or add an LM or a full n-gram scorer")
         self._pinned = None
         self._copy_q = None        # the queue the per-token records leave on (created with the first captured search)
         self._captured = None      # the captured step of the last batch shape (buffers + hipGraph), re-used while the shape repeats
@@ -360,7 +372,17 @@ class BatchBeamSearch:
     @property
     def scorers(self):
         """names of the scorers the search runs (espnet's keys)"""
-        return tuple(k for k, on in (("decoder", self.has_dec), ("ctc", self.has_ctc), ("length_bonus", True), ("lm", self.has_lm)) if on)
+        return tuple(k for k, on in (("decoder", self.has_dec), ("ctc", self.has_ctc), ("length_bonus", True), ("lm", self.has_lm),
+                                     ("ngram", self.has_ngram)) if on)
+
+    @property
+    def has_ngram(self):
+        return self.ngram is not None and self.w_ngram != 0.0
+
+    @property
+    def _ngram_part(self):
+        """the n-gram behind the pre-beam, on its candidates alone; without pre-beam "part" is "full" (every token is a candidate)"""
+        return self.has_ngram and self.ngram_scorer == "part" and self.pre_beam
 
     @property
     def _ctc_all_tokens(self):
@@ -397,14 +419,16 @@ class BatchBeamSearch:
             self.dec_step.weights.sync()
         if self.has_lm:
             self.lm_step.sync_weights()
+        if self.has_ngram and self.ngram.device != dev:
+            raise ValueError(f"the n-gram's tables are on {self.ngram.device}, the encoder outputs on {dev}: move them with NgramLM.to(device)")
         # scorers {ctc, length_bonus} without pre-beam: the whole search is one launch where the beam's lattice fits a workgroup's LDS
-        if self._ctc_all_tokens and not self.has_lm and CTC_SEARCH_FUSED and ops.ctc_beam_search_ok(self.K, self.V, T):
+        if self._ctc_all_tokens and not self.has_lm and not self.has_ngram and CTC_SEARCH_FUSED and ops.ctc_beam_search_ok(self.K, self.V, T):
             self._search_one_launch(enc, enc_lens, host)
         else:
             # A captured step is tied to its buffers, not to a batch: while the shape (utterances, frames, token budget) repeats -
             # a stream of 4 s clips - the buffers are refilled in place and the hipGraph of the previous call is replayed; capture
             # and warm-up were 8-10 ms of a 95 ms batch-1 search.
-            key = (U, T, D, host.steps, str(dev), self.scorers)
+            key = (U, T, D, host.steps, str(dev), self.scorers, self._ngram_part)
             cap = self._captured
             if GRAPH_STEP and cap is not None and cap.key == key:
                 self._refill(cap, enc, enc_lens, host)
@@ -501,7 +525,9 @@ class BatchBeamSearch:
         else:
             sd, sdyn, cand_all = dyn.step, (dyn.step,), dyn.cand_all
         # the CTC scores of every token beside the scorers and the beam update behind them in one launch (CTC_BESIDE_SCORERS)
-        spec = dyn is not None and CTC_BESIDE_SCORERS and ops.beam_select_topk_ok(self.K, self.V) and self.C <= self.V
+        # (an n-gram behind the pre-beam needs the candidates before the weighted sum: the launches behind the scorers one by one)
+        spec = (dyn is not None and CTC_BESIDE_SCORERS and ops.beam_select_topk_ok(self.K, self.V) and self.C <= self.V
+                and not self._ngram_part)
         z_lm = None
         if has_lm:                   # the two scorers are independent chains of small launches: the LM runs beside the decoder
             with ops.BranchScope(enabled=SCORERS_PARALLEL) as br:
@@ -513,23 +539,30 @@ class BatchBeamSearch:
             ctc = self._ctc_prefix(b, i, sd, cand_all)
         # full = w_dec * decoder + w_lm * lm + w_len (LengthBonus: 1 per token), summed by the scorers' last launches
         dec = self.dec_step.step(i, b.tok, b.anc, sdyn, alpha=self.w_dec, add=0.0 if has_lm else self.w_len) if has_dec else None
+        if self.has_ngram and not self._ngram_part:
+            # the n-gram's weighted row lands on the decoder's (behind its chain, on its queue); without decoder it opens the row and
+            # carries the length bonus where no LM launch follows to carry it
+            dec = ops.ngram_score(self.ngram, b.yseq, i, out=dec, alpha=self.w_ngram, add=0.0 if (has_dec or has_lm) else self.w_len,
+                                  accumulate=has_dec, step_dev=sd)
         if has_lm:
             br.join()
         if spec:
             cand, r_new, psi, psi_abs, eos_s, eos_abs = ctc
-            top = ops.beam_select_topk(dec, z_lm, self.w_lm, self.w_len if (has_lm or not has_dec) else 0.0, psi, psi_abs, eos_s, eos_abs,
+            top = ops.beam_select_topk(dec, z_lm, self.w_lm, self.w_len if (has_lm or dec is None) else 0.0, psi, psi_abs, eos_s, eos_abs,
                                        b.s_prev, b.score, self.eos, self.w_ctc, self.K, self.C)
             return self._commit(b, dyn, top, cand, r_new, psi_abs)
         full = self._full_row(b, dec, z_lm)
         if has_ctc:
             ctc = self._ctc_prefix(b, i, sd, cand_all, full)
+        if self._ngram_part:             # behind the pre-beam: onto its candidates alone (the refusal above: ``full`` is a row of this step)
+            ops.ngram_score(self.ngram, b.yseq, i, out=full, alpha=self.w_ngram, accumulate=True, step_dev=sd, cand=ctc[0])
         if dyn is not None:
             return self._beam_update_captured(b, dyn, full, *ctc)
         return self._beam_update_eager(b, i, full, *ctc)
 
     def _full_row(self, b, dec, z_lm):
-        """the full scorers' weighted row [N, V] behind their chains: the LM's log-softmax lands on the decoder's row; no decoder
-        and no LM: the length bonus alone"""
+        """the full scorers' weighted row [N, V] behind their chains: the LM's log-softmax lands on the decoder's row (``dec``: the
+        decoder's and / or the full n-gram's); no decoder, no n-gram and no LM: the length bonus alone"""
         if dec is None:
             return b.full_const if z_lm is None else ops.log_softmax_rows(z_lm, alpha=self.w_lm, add=self.w_len)
         if z_lm is not None:
@@ -785,7 +818,8 @@ class Speech2Text:
 
     def __init__(self, asr_model, lm=None, beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
                  penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0,
-                 skip_zero_weight: bool = False, timestamps: bool = False, frame_seconds: float = 0.04):
+                 skip_zero_weight: bool = False, timestamps: bool = False, frame_seconds: float = 0.04,
+                 ngram_file: Optional[str] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9):
         # timestamps: every returned hypothesis is aligned to its utterance's CTC posteriors after the search (one launch of
         # tavsr_ctc_align for the whole batch) and its result tuple gains a fifth element, the record of utils/timestamps.py.
         # frame_seconds: one encoder frame - 10 ms hop x 4 subsampling for audio, 25 fps for video: 0.04 s in every shipped recipe.
@@ -797,8 +831,14 @@ class Speech2Text:
         self.asr_model = asr_model.eval()
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
+        # ngram_file: an ARPA text file (a KenLM binary is not read); its tables go to the model's device once, here
+        ngram = None
+        if ngram_file is not None and ngram_weight != 0.0:
+            from ..lm.ngram import NgramLM
+            ngram = NgramLM.from_arpa(ngram_file, asr_model.token_list, next(asr_model.parameters()).device)
         self.beam_search = BatchBeamSearch(asr_model, lm, beam_size, ctc_weight, lm_weight, penalty, maxlenratio, minlenratio,
-                                           skip_zero_weight=skip_zero_weight)
+                                           skip_zero_weight=skip_zero_weight, ngram=ngram, ngram_weight=ngram_weight,
+                                           ngram_scorer=ngram_scorer)
         self.encode = CapturedEncode(self.asr_model)
 
     @torch.no_grad()

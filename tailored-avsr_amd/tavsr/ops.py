@@ -2127,6 +2127,29 @@ def log_softmax_rows(x, V=None, out=None, alpha=1.0, add=0.0, accumulate=False):
     return out
 
 
+def ngram_score(lm, yseq, step, out=None, alpha=1.0, add=0.0, accumulate=False, step_dev=None, cand=None):
+    """out = (out if accumulate else 0) + alpha * (n-gram log10 scores of every token) + add for the hypotheses yseq[:, :step + 1]
+    (tavsr_ngram_score; see include/tavsr.h for the semantics).  ``lm``: tavsr.lm.ngram.NgramLM on the device of ``yseq``;
+    ``step_dev`` (int32 device scalar) replaces ``step`` (graph replays); ``cand`` int64 [N, C]: only these tokens of every row are
+    written (``out`` must then be given)."""
+    N, L = yseq.shape
+    V = lm.word_map.numel()
+    require_cuda(lm.word, lm.logp, lm.backoff, lm.child_begin, lm.word_map, yseq, out, step_dev, cand)
+    assert yseq.dtype == torch.int64 and yseq.stride(1) == 1
+    assert step_dev is None or step_dev.dtype == torch.int32
+    assert cand is None or (cand.dtype == torch.int64 and cand.is_contiguous() and cand.shape[0] == N and out is not None)
+    assert not accumulate or out is not None
+    if out is None:
+        out = torch.empty((N, V), dtype=f32, device=yseq.device)
+    assert out.dtype == f32 and out.shape == (N, V) and out.stride(1) == 1
+    check(lib().tavsr_ngram_score(ptr(lm.word), ptr(lm.logp), ptr(lm.backoff), ptr(lm.child_begin), lm.n_unigrams, lm.order,
+                                  lm.bos_word, lm.unk_logp, ptr(lm.word_map), ptr(yseq), yseq.stride(0), L,
+                                  0 if step_dev is not None else int(step), ptr(step_dev), ptr(cand),
+                                  0 if cand is None else cand.shape[1], alpha, add, int(bool(accumulate)), ptr(out), out.stride(0),
+                                  N, V, stream()), "tavsr_ngram_score")
+    return out
+
+
 def beam_combine(full, cand, psi, psi_abs, eos_s, eos_abs, s_prev, score, eos, w_ctc):
     """weighted = full + w_ctc * (partial CTC scorer row) + score; fixes psi_abs of <eos> candidates in place (tavsr.h).
     ``psi`` None: no CTC scorer - weighted = full + score, the other CTC operands are not read."""
