@@ -1056,6 +1056,53 @@ int tavsr_ctc_beam_search_ok(int32_t K, int32_t V, int32_t T);
 int tavsr_ctc_beam_search(const float* logp, const int64_t* lens, const int32_t* maxlen, int32_t* hist, int32_t* n_steps, int32_t U,
                           int32_t K, int32_t T, int32_t V, int32_t hist_steps, int32_t sos, int32_t eos, int32_t blank, float w_ctc,
                           float add, int32_t end_detect, float d_end, tavsr_stream_t stream);
+/* Time-synchronous beam search (csrc/timesync.hip; espnet BeamSearchTimeSync, the reference's Speech2Text(time_sync=True),
+ * src/inference/avsr_inference.py:94, 257-275): a CTC prefix beam search walked frame by frame, the prefixes that enter the beam
+ * rescored by the decoder and the LM.  lpz [U][T][V] log-softmax of the CTC head, lens [U] frames, K beam, C pre-beam size (the tokens
+ * with p >= the C-th largest value of the frame, ties all kept, at most min(V, 2 C): more sets the utterance's overflow word), hyps
+ * start from (<sos>,).  One workgroup per utterance.
+ *   ws int32 [U][tavsr_timesync_ws(K, V, T, C)]: per utterance the beam (K slots; a member keeps its slot while it stays), the table of
+ *       the prefixes expanded in the previous frame (dp: key, p_nb, p_b - in LDS while a kernel runs), the trie of the prefixes that
+ *       ever entered the beam (parent, token per node; node 0 is (<sos>,); at most 1 + K T nodes) and its open-addressing table keyed
+ *       by (parent node, token): a prefix has ONE node for the whole utterance, however often it leaves the beam and comes back.
+ *       tavsr_timesync_ws_offset(.., which): word offset inside an utterance's block of 0: order [K] (slot per rank, -1: none), 1: node [K]
+ *       (per slot), 2: score [K] (per slot, fp32), 3: misc (beam members, nodes, overflow flag, ...), 4: parent [nodes], 5: token [nodes];
+ *       6: nodes per utterance (1 + K T), 7: the candidate cap.  tavsr_timesync_ok: 1 when the shape is taken (K <= 64, the frame's tables
+ *       within one workgroup's 160 KiB of LDS, (3 + K T) V < 2^31); the entries return TAVSR_EUNSUPPORTED before any launch otherwise.
+ *   tavsr_timesync_init  : the state before frame 0 and *frame_dev = 0 (frame_dev nullable).  With the scorers' operands given
+ *       (tok int64 [U K], pos / nkeys int32 [U K], anc int32 [U K][ld_anc], ld_anc >= T + 1): every tok = <sos>, slot 0 of every
+ *       utterance is new (nkeys 1, pos 0, anc[0] = its node's pool row u (1 + K T)) - (<sos>,) is scored once before frame 0.
+ *   tavsr_timesync_step  : frame *frame_dev of every utterance (nothing for an utterance whose lens[u] <= *frame_dev; the counter is not
+ *       advanced).  First the rows of the slots that were new (nkeys > 0) move from dec_new / lm_new [U K][V] to dec_rows / lm_rows and
+ *       nkeys becomes 0; then steps 1 - 5 of the search: candidates, expansion with the merge of equal prefixes, joint score
+ *       w_ctc logaddexp(p_nb, p_b) + w_dec sum(decoder) + w_lm sum(lm) + pen (tokens), the K best.  For every slot that is new the kernel
+ *       writes tok, pos = depth, nkeys = depth + 1 and anc = the pool rows of its ancestors, its own (u (1 + K T) + node) last.
+ *       dec_new / dec_rows NULL: no decoder term; lm_new / lm_rows NULL: no LM term; tok .. anc_tmp NULL (then no scorer rows either):
+ *       nothing is written for scorers.  A term of weight 0 is skipped.  anc_tmp: scratch of anc's shape.
+ *   tavsr_timesync_search: every frame of every utterance in ONE launch, for a search without decoder and LM: the same device code as
+ *       tavsr_timesync_step with NULL scorer operands, the same bits. */
+int tavsr_timesync_ok(int32_t K, int32_t V, int32_t T, int32_t C);
+int64_t tavsr_timesync_ws(int32_t K, int32_t V, int32_t T, int32_t C);
+int32_t tavsr_timesync_ws_offset(int32_t K, int32_t V, int32_t T, int32_t C, int32_t which);
+int tavsr_timesync_init(int32_t* ws, int64_t* tok, int32_t* pos, int32_t* nkeys, int32_t* anc, int64_t ld_anc, int32_t* frame_dev,
+                        int32_t U, int32_t K, int32_t V, int32_t T, int32_t C, int32_t sos, int32_t blank, tavsr_stream_t stream);
+int tavsr_timesync_step(const float* lpz, const int64_t* lens, int32_t* ws, const float* dec_new, float* dec_rows,
+                        const float* lm_new, float* lm_rows, int64_t* tok, int32_t* pos, int32_t* nkeys, int32_t* anc,
+                        int32_t* anc_tmp, int64_t ld_anc, const int32_t* frame_dev, int32_t U, int32_t K, int32_t V, int32_t T,
+                        int32_t C, int32_t sos, int32_t blank, float w_ctc, float w_dec, float w_lm, float pen,
+                        tavsr_stream_t stream);
+int tavsr_timesync_search(const float* lpz, const int64_t* lens, int32_t* ws, int32_t U, int32_t K, int32_t V, int32_t T, int32_t C,
+                          int32_t sos, int32_t blank, float w_ctc, float pen, tavsr_stream_t stream);
+/* Scorer launches whose rows sit at different depths (the time-synchronous search: a frame's new prefixes have different lengths):
+ *   tavsr_tree_attn_rows: tavsr_tree_attn_step with nkeys_row [N] int32 keys per row (clamped to max_keys <= 1024, <= ld_anc).  A row
+ *       with 0 keys is skipped: nothing of it is read, its output is left alone.  k_new / v_new [N][H dk] (row stride ldq, required)
+ *       are the row's last key / value; they are written to the pool row anc[n][nkeys_row[n] - 1].
+ *   tavsr_embed_pe_rows : tavsr_embed_pe_step with a position per row: out[n] = table[ids[n]] * scale + pe[min(max(pos[n], 0), L - 1)] */
+int tavsr_tree_attn_rows(const float* q, int64_t ldq, const float* kpool, const float* vpool, int64_t ldkv, const int32_t* anc,
+                         int64_t ld_anc, const int32_t* nkeys_row, int32_t max_keys, float* out, int64_t ldo, int32_t N, int32_t H,
+                         int32_t dk, float scale, const float* k_new, const float* v_new, tavsr_stream_t stream);
+int tavsr_embed_pe_rows(const int64_t* ids, const float* table, const float* pe, float scale, float* out, int64_t N, int32_t L,
+                        int32_t D, const int32_t* pos, tavsr_stream_t stream);
 /* N-gram LM scorer of the beam search (the reference's `ngram` scorer: src/inference/avsr_inference.py:166-178 builds espnet's
  * NgramFullScorer / NgramPartScorer over a KenLM model; here: ARPA tables in device memory, tavsr/lm/ngram.py:NgramLM builds them).
  * Tables - a forward trie in CSR form over ONE numbering of all n-grams: nodes 0 .. n_unigrams - 1 are the unigrams (node = word id),

@@ -205,12 +205,17 @@ class _DecoderStep:
         for L, kv in zip(self.layers, self.memkv):
             ops.linear(mem2, L["wkv2"], L["bkv2"], out=kv, ldc=kv.stride(0))
 
-    def step(self, i, tok, anc, dyn=None, **score):
+    def step(self, i, tok, anc, dyn=None, rows=None, **score):
         """tok [N] last tokens, anc int32 [N, >= i+1] (column i already points at this step's rows) -> logp [N, V].
         ``dyn`` = (step_dev,): the step index - and with it the positional row - is read from a device buffer (``i`` is then the
-        pool capacity in steps), so the launches can be captured once and replayed for every step."""
+        pool capacity in steps), so the launches can be captured once and replayed for every step.
+        ``rows`` = (nkeys_row, pos_row, max_keys), int32 [N] each: rows at DIFFERENT depths (the time-synchronous search) - row n embeds
+        position pos_row[n] and attends to its own nkeys_row[n] ancestors; a row with 0 keys does no attention and its result is not
+        meant to be read (``i`` / ``dyn`` are not used)."""
         N, D, H, dk, U, T, K = self.N, self.D, self.H, self.dk, self.U, self.T, self.K
-        if dyn is None:
+        if rows is not None:
+            x = ops.embed_pe_rows(tok, self.emb, self.pe, self.xscale, rows[1])
+        elif dyn is None:
             x = ops.embed_pe(tok.view(N, 1), self.emb, self.pe[i:i + 1].contiguous(), self.xscale).view(N, D)
         else:      # the positional row of the device-side step counter: read by the embedding launch itself
             x = ops.embed_pe(tok.view(N, 1), self.emb, self.pe, self.xscale, step_dev=dyn[0]).view(N, D)
@@ -218,9 +223,13 @@ class _DecoderStep:
         for li, L in enumerate(self.layers):
             qkv = _ln_linear(x, L["n1"], L["wqkv"], L["bqkv"])
             # this step's keys / values are the last key of every hypothesis: the attention launch appends them to the pools
-            a = ops.tree_attn_step(qkv[:, :D], self.kpool[li], self.vpool[li], anc, i + 1 if dyn is None else i, H, dk,
-                                   step_dev=None if dyn is None else dyn[0], k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:],
-                                   group=TREE_GROUP * self.K)
+            if rows is not None:
+                a = ops.tree_attn_rows(qkv[:, :D], self.kpool[li], self.vpool[li], anc, rows[0], rows[2], H, dk, qkv[:, D:2 * D],
+                                       qkv[:, 2 * D:])
+            else:
+                a = ops.tree_attn_step(qkv[:, :D], self.kpool[li], self.vpool[li], anc, i + 1 if dyn is None else i, H, dk,
+                                       step_dev=None if dyn is None else dyn[0], k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:],
+                                       group=TREE_GROUP * self.K)
             x = _linear_res(a, L["wo"], L["bo"], x, ln_next=L["n2"])
             q2 = _ln_linear(x, L["n2"], L["wq2"], L["bq2"])
             # source attention: the K slots of an utterance are K query rows against that utterance's memory
@@ -290,7 +299,8 @@ class _LMStep:
             self.in_table.copy_(self._input_table())
         self._table_ver = ver
 
-    def step(self, i, tok, anc, dyn=None, logits_only=False, **score):
+    def step(self, i, tok, anc, dyn=None, logits_only=False, rows=None, **score):
+        """``rows``: as ``_DecoderStep.step`` (the LM embeds no position: its key counts alone are used)"""
         N, D, H, dk = self.N, self.D, self.H, self.dk
         lm = self.lm
         # the token's row of the input table is gathered by the first layer's launches themselves where the one-launch Linear
@@ -304,9 +314,13 @@ class _LMStep:
             else:
                 qkv = _ln_linear(h, L["n1"], L["wqkv"], L["bqkv"])
             # this step's keys / values are the last key of every hypothesis: the attention launch appends them to the pools
-            a = ops.tree_attn_step(qkv[:, :D], self.kpool[li], self.vpool[li], anc, i + 1 if dyn is None else i, H, dk,
-                                   step_dev=None if dyn is None else dyn[0], k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:],
-                                   group=TREE_GROUP * self.K)
+            if rows is not None:
+                a = ops.tree_attn_rows(qkv[:, :D], self.kpool[li], self.vpool[li], anc, rows[0], rows[2], H, dk, qkv[:, D:2 * D],
+                                       qkv[:, 2 * D:])
+            else:
+                a = ops.tree_attn_step(qkv[:, :D], self.kpool[li], self.vpool[li], anc, i + 1 if dyn is None else i, H, dk,
+                                       step_dev=None if dyn is None else dyn[0], k_new=qkv[:, D:2 * D], v_new=qkv[:, 2 * D:],
+                                       group=TREE_GROUP * self.K)
             if li == 0 and fold:
                 h = ops.rowlin(a, L["wo"], L["bo"], res=self.in_table, res_gather=tok)
             else:
@@ -819,7 +833,7 @@ class Speech2Text:
     def __init__(self, asr_model, lm=None, beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
                  penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0,
                  skip_zero_weight: bool = False, timestamps: bool = False, frame_seconds: float = 0.04,
-                 ngram_file: Optional[str] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9):
+                 ngram_file: Optional[str] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9, time_sync: bool = False):
         # timestamps: every returned hypothesis is aligned to its utterance's CTC posteriors after the search (one launch of
         # tavsr_ctc_align for the whole batch) and its result tuple gains a fifth element, the record of utils/timestamps.py.
         # frame_seconds: one encoder frame - 10 ms hop x 4 subsampling for audio, 25 fps for video: 0.04 s in every shipped recipe.
@@ -831,6 +845,14 @@ class Speech2Text:
         self.asr_model = asr_model.eval()
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
+        self.encode = CapturedEncode(self.asr_model)
+        # time_sync: espnet's BeamSearchTimeSync in place of the label-synchronous search (avsr_inference.py:257-275;
+        # inference/timesync.py); results, nbest and timestamps as for the other search
+        if time_sync:
+            from .timesync import BeamSearchTimeSync
+            self.beam_search = BeamSearchTimeSync(asr_model, lm, beam_size, ctc_weight, lm_weight, penalty, maxlenratio=maxlenratio,
+                                                  minlenratio=minlenratio, ngram=ngram_file if ngram_weight != 0.0 else None)
+            return
         # ngram_file: an ARPA text file (a KenLM binary is not read); its tables go to the model's device once, here
         ngram = None
         if ngram_file is not None and ngram_weight != 0.0:
@@ -839,7 +861,6 @@ class Speech2Text:
         self.beam_search = BatchBeamSearch(asr_model, lm, beam_size, ctc_weight, lm_weight, penalty, maxlenratio, minlenratio,
                                            skip_zero_weight=skip_zero_weight, ngram=ngram, ngram_weight=ngram_weight,
                                            ngram_scorer=ngram_scorer)
-        self.encode = CapturedEncode(self.asr_model)
 
     @torch.no_grad()
     def __call__(self, *batch):

@@ -2262,6 +2262,94 @@ def ctc_beam_search(logp, lens, maxlen, hist, n_steps, K, sos, eos, w_ctc, add, 
           "tavsr_ctc_beam_search")
 
 
+# ---------------------------------------------------------------------------------------------- time-synchronous search
+def timesync_ok(K, V, T, C) -> bool:
+    """does the time-synchronous search take this (beam, vocabulary, frames, pre-beam)?  The library's answer (include/tavsr.h)."""
+    return bool(lib().tavsr_timesync_ok(int(K), int(V), int(T), int(C)))
+
+
+def timesync_ws(K, V, T, C):
+    """(int32 words of an utterance's workspace, {name: word offset}) of ``tavsr_timesync_*``; raises where the shape is not taken"""
+    words = int(lib().tavsr_timesync_ws(int(K), int(V), int(T), int(C)))
+    if words <= 0:
+        raise L.TavsrError(f"tavsr_timesync: beam {K}, {V} tokens, {T} frames, pre-beam {C} is not supported (tavsr_timesync_ok): "
+                         "beam <= 64, the frame's tables within one workgroup's LDS, (3 + beam * frames) * tokens < 2^31")
+    names = ("order", "node", "score", "misc", "parent", "token", "nodes", "cand_cap")
+    return words, {n: int(lib().tavsr_timesync_ws_offset(int(K), int(V), int(T), int(C), i)) for i, n in enumerate(names)}
+
+
+def _ts_scorer_ptrs(sc):
+    """(tok int64 [N], pos, nkeys int32 [N], anc int32 [N, ld]) or None -> the operands' addresses and ld"""
+    if sc is None:
+        return (None, None, None, None), 0
+    tok, pos, nkeys, anc = sc
+    require_cuda(tok, pos, nkeys, anc)
+    assert tok.dtype == torch.int64 and pos.dtype == nkeys.dtype == anc.dtype == torch.int32 and anc.is_contiguous()
+    return (ptr(tok), ptr(pos), ptr(nkeys), ptr(anc)), anc.stride(0)
+
+
+def timesync_init(ws, U, K, V, T, Cn, sos, blank=0, scorer=None, frame_dev=None):
+    """the state before frame 0 (tavsr_timesync_init); ``scorer`` = (tok, pos, nkeys, anc): slot 0 of every utterance is new"""
+    require_cuda(ws)
+    assert ws.dtype == torch.int32 and ws.is_contiguous() and ws.shape[0] == U
+    ptrs, ld = _ts_scorer_ptrs(scorer)
+    check(lib().tavsr_timesync_init(ptr(ws), *ptrs, ld, ptr(frame_dev), U, int(K), V, T, int(Cn), int(sos), int(blank), stream()),
+          "tavsr_timesync_init")
+
+
+def timesync_step(lpz, lens, ws, frame_dev, K, Cn, sos, w_ctc, w_dec, w_lm, pen, dec=None, lm=None, scorer=None, anc_tmp=None, blank=0):
+    """one frame of every utterance (tavsr_timesync_step).  ``dec`` / ``lm`` = (new rows, kept rows) [U K, V] or None."""
+    U, T, V = lpz.shape
+    require_cuda(lpz, lens, ws, frame_dev)
+    assert lpz.is_contiguous() and lpz.dtype == f32 and lens.dtype == torch.int64 and frame_dev.dtype == torch.int32
+    for pair in (dec, lm):
+        assert pair is None or all(t.is_contiguous() and t.shape == (U * K, V) and t.dtype == f32 for t in pair)
+    ptrs, ld = _ts_scorer_ptrs(scorer)
+    dn, dr = (None, None) if dec is None else dec
+    ln, lr = (None, None) if lm is None else lm
+    check(lib().tavsr_timesync_step(ptr(lpz), ptr(lens), ptr(ws), ptr(dn), ptr(dr), ptr(ln), ptr(lr), *ptrs, ptr(anc_tmp), ld,
+                                    ptr(frame_dev), U, int(K), V, T, int(Cn), int(sos), int(blank), w_ctc, w_dec, w_lm, pen, stream()),
+          "tavsr_timesync_step")
+
+
+def timesync_search(lpz, lens, ws, K, Cn, sos, w_ctc, pen, blank=0):
+    """every frame of every utterance in one launch, no scorer rows (tavsr_timesync_search)"""
+    U, T, V = lpz.shape
+    require_cuda(lpz, lens, ws)
+    assert lpz.is_contiguous() and lpz.dtype == f32 and lens.dtype == torch.int64
+    check(lib().tavsr_timesync_search(ptr(lpz), ptr(lens), ptr(ws), U, int(K), V, T, int(Cn), int(sos), int(blank), w_ctc, pen, stream()),
+          "tavsr_timesync_search")
+
+
+TREE_ROWS_MAX_KEYS = 1024      # keys per row that tavsr_tree_attn_rows takes (its per-wave LDS arrays; include/tavsr.h)
+
+
+def tree_attn_rows(q, kpool, vpool, anc, nkeys_row, max_keys, H, dk, k_new, v_new, out=None):
+    """``tree_attn_step`` with a key count per row (int32 [N]): a row with 0 keys is skipped and its output row left alone; the row's
+    own key / value goes to the pool row its last ancestor entry names (tavsr_tree_attn_rows)"""
+    N = q.shape[0]
+    require_cuda(q, kpool, vpool, anc, nkeys_row, k_new, v_new)
+    assert anc.dtype == torch.int32 and nkeys_row.dtype == torch.int32 and kpool.stride(0) == vpool.stride(0)
+    assert k_new.stride(0) == q.stride(0) and v_new.stride(0) == q.stride(0)
+    if out is None:
+        out = empty(N, H * dk, like=q)
+    check(lib().tavsr_tree_attn_rows(ptr(q), q.stride(0), ptr(kpool), ptr(vpool), kpool.stride(0), ptr(anc), anc.stride(0),
+                                     ptr(nkeys_row), int(max_keys), ptr(out), out.stride(0), N, H, dk, 1.0 / (dk ** 0.5), ptr(k_new),
+                                     ptr(v_new), stream()), "tavsr_tree_attn_rows")
+    return out
+
+
+def embed_pe_rows(ids, table, pe, scale, pos):
+    """table[ids] * scale + pe[pos]: ids int64 [N], pos int32 [N] (clamped to pe's rows) -> [N, D] (tavsr_embed_pe_rows)"""
+    require_cuda(ids, table, pe, pos)
+    N, D = ids.numel(), table.shape[1]
+    assert pos.dtype == torch.int32 and pos.numel() == N and pe.is_contiguous() and pe.shape[1] == D and table.is_contiguous()
+    out = empty(N, D, like=table)
+    check(lib().tavsr_embed_pe_rows(ptr(ids), ptr(table), ptr(pe), scale, ptr(out), N, pe.shape[0], D, ptr(pos), stream()),
+          "tavsr_embed_pe_rows")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- dropout
 # The generator state is ONE uint64 per device, resident in HBM.  ``rng_step_begin`` advances it with a kernel (so a
 # captured step graph draws new masks at every replay), writes the advanced value into a fresh one-element tensor that
