@@ -746,6 +746,92 @@ int tavsr_ctc_align(const float* logits, int64_t ld_t, int64_t ld_b, const int64
                     tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Transducer (espnet2 asr/decoder/transducer_decoder.py, asr_transducer/joint_network.py, warp-transducer's RNNTLoss with
+ * reduction="mean" and fastemit_lambda = 0, espnet2 asr/transducer/beam_search_transducer.py greedy_search).  csrc/rnnt.hip.
+ *
+ * LSTM, one layer, batch first, torch's parameter layout (weight_ih [4H][I], weight_hh [4H][H], gate order i, f, g, o).
+ * The input products xg [B][L][4H] = x W_ih^T (row stride ld_xg, no bias) are one tavsr_gemm; these kernels do the recurrence.
+ * A workgroup owns tavsr_lstm_rows_per_wg() batch rows and all 4H gate columns for all steps; the rows are independent, so
+ * there is no barrier, cooperative launch or flag between workgroups.  H % 4 == 0 and H <= 1024, else TAVSR_EUNSUPPORTED.
+ *   lstm_wt  : w_hh_t [H][4H] = w_hh^T, the layout lstm_fwd / lstm_step stream (once per call, or once per search).
+ *   lstm_fwd : for t < lens[b] (lens NULL: every step): gates = act(xg[b][t] + b_ih + b_hh + h W_hh^T), c = f c + i g,
+ *              h = o tanh(c); a padded step leaves (h, c) alone.  h0 / c0 [B][H] (NULL: zeros).  Outputs, nullable but hN /
+ *              cN: y [B][L][H] = h after the step (0 at padded steps), hprev [B][L][H] = h before the step, c_all [B][L][H]
+ *              = c after the step, gates [B][L][4H] = the activated i, f, g, o (0 at padded steps), hN / cN [B][H] = the
+ *              state after the last step.
+ *   lstm_bwd : the reverse walk in the same partition.  dy [B][L][H] (gradient of y; NULL: zeros), dhN / dcN [B][H]
+ *              (nullable).  dgates [B][L][4H] = the gradient of the gate pre-activations (0 at padded steps): the operand of
+ *              dx = dgates W_ih, dW_ih = dgates^T x, dW_hh = dgates^T hprev (tavsr_gemm) and of both bias gradients (its
+ *              column sums).  dh0 / dc0 [B][H] nullable.
+ *   lstm_step: lstm_fwd with L = 1 for N hypothesis rows, states in and out (h_out may be h_in, c_out may be c_in: a
+ *              workgroup reads its rows before it writes them).  commit (nullable) [N] bytes: a row with commit == 0 keeps
+ *              its state.  The kernel and the order of its sums are lstm_fwd's: a step is bit-equal to that step of
+ *              lstm_fwd.  Nothing is read on the host: capturable.
+ *
+ * Joint network and loss over the lattice rows n = (b * T + t) * U1 + u, U1 = (longest label sequence) + 1.  Row n is live
+ * when t < tlens[b] and u <= ulens[b]; a dead row is neither read by the loss nor given a gradient.  e [B][T][J] =
+ * lin_enc(enc), d [B][U1][J] = lin_dec(dec), w_out [V][J], b_out [V] (nullable), y [B][ld_y] int32 labels.
+ *   rnnt_mask_rows : out[b][r][:] = r < lens[b] + extra ? x[b][r][:] : 0 over [B][Tn][D] - the rows the joint's Linears take
+ *                    (a padded row may hold anything, NaN included; it must not reach a product).
+ *   rnnt_joint_rows: in chunks of `chunk` rows: z = tanh(e[b][t] + d[b][u]) (dead rows 0), logits = z W_out^T + b_out
+ *                    (tavsr_gemm into the workspace), and per row three floats: lse[n] = logsumexp(logits), lp_blank[n] =
+ *                    logits[blank] - lse, lp_label[n] = logits[y[b][u]] - lse (0 at u == ulens[b] and in dead rows).  The
+ *                    [B][T][U1][V] tensor is never resident: ws >= tavsr_rnnt_ws(B, T, U1, J, V, chunk, 0) floats.
+ *   rnnt_lattice   : one workgroup per utterance: alpha and beta over tlens[b] x (ulens[b] + 1) in log space along
+ *                    anti-diagonals.  nll[b] = -(alpha[T_b-1][U_b] + lp_blank[T_b-1][U_b]); per node occ = exp(alpha + beta
+ *                    - ll), p_blank = exp(alpha + lp_blank + beta[t+1][u] - ll) (the final blank at (T_b-1, U_b): exp(alpha +
+ *                    lp_blank - ll)), p_label = exp(alpha + lp_label + beta[t][u+1] - ll); 0 in dead nodes.  Every element of
+ *                    the outputs [B][T][U1] is written.  U_b = 0 and T_b = 1 are valid; T_b <= 0 gives nll = 0.  ws == NULL
+ *                    keeps alpha and beta in LDS (TAVSR_EUNSUPPORTED when tavsr_rnnt_lattice_lds_ok(T, U1) is 0); ws !=
+ *                    NULL (>= tavsr_rnnt_lattice_ws(B, T, U1) floats) keeps them there at any size.  One kernel body runs
+ *                    both routes: their results are bit-identical.  One launch, nothing read on the host.
+ *   rnnt_joint_grad: per chunk the logits again, then in place G[n][v] = gscale[0] * inv_b * (occ * softmax - [v == blank]
+ *                    p_blank - [v == label] p_label) (gscale: the upstream gradient, device data; NULL: 1), dz = G W_out,
+ *                    dW_out += G^T z, db_out += column sums of G (tavsr_gemm; the parts are added chunk by chunk in row
+ *                    order), dz *= 1 - z^2, de[b][t] += sum_u dz, dd[b][u] += sum_t dz: every element has one owner per
+ *                    launch and the launches are ordered - no atomics, the same bits every run.  de [B][T][J], dd
+ *                    [B][U1][J], dw_out [V][J], db_out [V] (nullable) are overwritten.  ws >= tavsr_rnnt_ws(..., 1) floats.
+ * Greedy search (one replayed graph per encoder frame; `frame` is an int32 in device memory):
+ *   rnnt_frame_z    : z[b] = tanh(e[b][min(frame, T - 1)] + d[b]), d [B][J].
+ *   rnnt_greedy_pick: per utterance the log-softmax and argmax (lowest index on ties) of logits[b][:V].  Where frame <
+ *                     tlens[b], the argmax is not blank and hyp_len[b] < ld_hyp: hyp[b][hyp_len[b]++] = argmax, score[b] += its
+ *                     log-probability, tok[b] = argmax, commit[b] = 1; else commit[b] = 0.  Then frame += 1.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_lstm_rows_per_wg(void);
+int tavsr_lstm_wt(const float* w_hh, float* w_hh_t, int32_t H, tavsr_stream_t stream);
+int tavsr_lstm_fwd(const float* xg, int64_t ld_xg, const float* w_hh_t, const float* b_ih, const float* b_hh,
+                   const float* h0, const float* c0, const int64_t* lens, float* y, float* hprev, float* c_all,
+                   float* gates, float* hN, float* cN, int32_t B, int32_t L, int32_t H, tavsr_stream_t stream);
+int tavsr_lstm_bwd(const float* dy, const float* dhN, const float* dcN, const float* w_hh, const float* c0,
+                   const int64_t* lens, const float* c_all, const float* gates, float* dgates, float* dh0, float* dc0,
+                   int32_t B, int32_t L, int32_t H, tavsr_stream_t stream);
+int tavsr_lstm_step(const float* xg, int64_t ld_xg, const float* w_hh_t, const float* b_ih, const float* b_hh,
+                    const float* h_in, const float* c_in, const uint8_t* commit, float* h_out, float* c_out, int32_t N,
+                    int32_t H, tavsr_stream_t stream);
+int tavsr_rnnt_mask_rows(const float* x, const int64_t* lens, int32_t extra, float* out, int32_t B, int32_t Tn, int32_t D,
+                         tavsr_stream_t stream);
+int64_t tavsr_rnnt_ws(int32_t B, int32_t T, int32_t U1, int32_t J, int32_t V, int32_t chunk, int32_t grad);
+int tavsr_rnnt_joint_rows(const float* e, const float* d, const float* w_out, const float* b_out, const int32_t* y,
+                          int64_t ld_y, const int64_t* tlens, const int64_t* ulens, int32_t blank, float* lse,
+                          float* lp_blank, float* lp_label, float* ws, int32_t B, int32_t T, int32_t U1, int32_t J,
+                          int32_t V, int32_t chunk, tavsr_stream_t stream);
+int tavsr_rnnt_lattice_lds_ok(int32_t T, int32_t U1);
+int64_t tavsr_rnnt_lattice_ws(int32_t B, int32_t T, int32_t U1);
+int tavsr_rnnt_lattice(const float* lp_blank, const float* lp_label, const int64_t* tlens, const int64_t* ulens, float* nll,
+                       float* occ, float* p_blank, float* p_label, float* ws, int32_t B, int32_t T, int32_t U1,
+                       tavsr_stream_t stream);
+int tavsr_rnnt_joint_grad(const float* e, const float* d, const float* w_out, const float* b_out, const int32_t* y,
+                          int64_t ld_y, const int64_t* tlens, const int64_t* ulens, int32_t blank, const float* lse,
+                          const float* occ, const float* p_blank, const float* p_label, const float* gscale, float inv_b,
+                          float* de, float* dd, float* dw_out, float* db_out, float* ws, int32_t B, int32_t T, int32_t U1,
+                          int32_t J, int32_t V, int32_t chunk, tavsr_stream_t stream);
+int tavsr_rnnt_frame_z(const float* e, const float* d, const int32_t* frame, float* z, int32_t B, int32_t T, int32_t J,
+                       tavsr_stream_t stream);
+int tavsr_rnnt_greedy_pick(const float* logits, int64_t ldv, const int64_t* tlens, int32_t blank, int32_t* frame,
+                           int64_t* tok, uint8_t* commit, int64_t* hyp, int64_t ld_hyp, int32_t* hyp_len, float* score,
+                           int32_t B, int32_t V, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask-CTC decoding (src/models/maskctc_model.py:285-349, MaskCTCInference.forward), one workgroup per utterance,
  * no host value read or written (a decode loop is one stream of launches, capturable).  Integer outputs: bit-exact contract.
  *   maskctc_init: from the CTC logits (strides as ctc_greedy): per frame t < hlens[b] the argmax (ctc_greedy's rule) and

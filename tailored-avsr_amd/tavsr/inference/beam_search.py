@@ -846,6 +846,16 @@ class Speech2Text:
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
         self.encode = CapturedEncode(self.asr_model)
+        # a transducer model is searched by BeamSearchTransducer (avsr_inference.py:181-207): greedy only, beam_size=1 (inference/transducer.py)
+        self.beam_search_transducer = None
+        if getattr(asr_model, "use_transducer_decoder", False):
+            from .transducer import BeamSearchTransducer
+            if lm is not None or ngram_file is not None or time_sync:
+                raise ValueError("the transducer search takes no LM, n-gram file or time_sync (greedy search only: beam_size=1)")
+            self.beam_search_transducer = BeamSearchTransducer(asr_model.decoder, asr_model.joint_network, beam_size, nbest=nbest,
+                                                               token_list=asr_model.token_list)
+            self.beam_search = self.beam_search_transducer
+            return
         # time_sync: espnet's BeamSearchTimeSync in place of the label-synchronous search (avsr_inference.py:257-275;
         # inference/timesync.py); results, nbest and timestamps as for the other search
         if time_sync:
@@ -872,10 +882,11 @@ class Speech2Text:
         if isinstance(enc, tuple):
             enc = enc[0]
         results = []
+        last = None if self.beam_search_transducer is not None else -1      # a transducer hypothesis has no <eos> (avsr_inference.py:497)
         for hyps in self.beam_search.decode(enc, enc_lens, nbest=self.nbest):
             res = []
             for ys, sc in hyps:
-                token_int = [t for t in ys[1:-1] if t != 0]
+                token_int = [t for t in ys[1:last] if t != 0]
                 token = [self.asr_model.token_list[t] for t in token_int]
                 text = "".join(token).replace("<space>", " ")
                 res.append((text, token, token_int, (ys, sc)))

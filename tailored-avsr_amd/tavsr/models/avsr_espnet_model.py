@@ -32,7 +32,8 @@ class ESPnetAVSRModel(ESPnetASRModel):
                          joint_network=joint_network, aux_ctc=aux_ctc, ctc_weight=ctc_weight, interctc_weight=interctc_weight,
                          ignore_id=ignore_id, lsm_weight=lsm_weight, length_normalized_loss=length_normalized_loss,
                          report_cer=report_cer, report_wer=report_wer, sym_space=sym_space, sym_blank=sym_blank,
-                         sym_sos=sym_sos, sym_eos=sym_eos, lang_token_id=lang_token_id)
+                         sym_sos=sym_sos, sym_eos=sym_eos, lang_token_id=lang_token_id,
+                         transducer_multi_blank_durations=transducer_multi_blank_durations)
         del self.frontend
         self.acoustic_frontend, self.visual_frontend = acoustic_frontend, visual_frontend
         self.acoustic_embed, self.visual_embed = acoustic_embed, visual_embed

@@ -17,6 +17,7 @@ import torch
 from .. import functional as F_
 from .. import ops
 from ..ctc.ctc import CTC
+from ..functional_rnnt import RNNTLossFn
 
 
 def add_sos_eos(ys_pad, ys_lens, sos, eos, ignore_id):
@@ -152,8 +153,16 @@ class ESPnetASRModel(torch.nn.Module):
         assert 0.0 <= ctc_weight <= 1.0, ctc_weight
         assert 0.0 <= interctc_weight < 1.0, interctc_weight
         super().__init__()
-        if joint_network is not None or preencoder is not None or postencoder is not None:
-            raise ValueError("transducer / pre- / post-encoder branches are out of the hot path (no shipped config)")
+        if preencoder is not None or postencoder is not None:
+            raise ValueError("pre- / post-encoder branches are out of the hot path (no shipped config)")
+        self.use_transducer_decoder = joint_network is not None      # espnet_model.py:114-147
+        if self.use_transducer_decoder:
+            if transducer_multi_blank_durations:
+                raise ValueError("transducer_multi_blank_durations: the multi-blank transducer loss is not on the HIP path "
+                                 "(leave the list empty: the plain RNN-T loss)")
+            if decoder is None:
+                raise ValueError("a joint network needs a transducer decoder (decoder: transducer)")
+            self.joint_network = joint_network
         self.blank_id = token_list.index(sym_blank) if sym_blank in token_list else 0
         self.sos = token_list.index(sym_sos) if sym_sos in token_list else vocab_size - 1
         self.eos = token_list.index(sym_eos) if sym_eos in token_list else vocab_size - 1
@@ -165,7 +174,7 @@ class ESPnetASRModel(torch.nn.Module):
             self.encoder.interctc_use_conditioning = False
         if self.encoder.interctc_use_conditioning:       # espnet_model.py:109-112
             self.encoder.conditioning_layer = torch.nn.Linear(vocab_size, self.encoder.output_size())
-        self.decoder = decoder if ctc_weight < 1.0 else None
+        self.decoder = decoder if (ctc_weight < 1.0 or self.use_transducer_decoder) else None
         self.lsm_weight, self.length_normalized_loss = lsm_weight, length_normalized_loss
         self.error_calculator = (ErrorCalculator(self.token_list, sym_space, sym_blank, report_cer, report_wer)
                                  if (report_cer or report_wer) else None)
@@ -209,7 +218,8 @@ class ESPnetASRModel(torch.nn.Module):
         loss_ctc = loss_att = None
         # training: the CTC branch (projection, loss, their backward) is independent of the attention decoder - it is enqueued on
         # the side queue and runs beside the decoder, forward and (autograd replays a node on its forward queue) backward
-        br = ops.BranchScope(LOSS_BRANCH and self.training and encoder_out.is_cuda and self.ctc_weight not in (0.0, 1.0))
+        beside = self.ctc_weight != 0.0 if self.use_transducer_decoder else self.ctc_weight not in (0.0, 1.0)
+        br = ops.BranchScope(LOSS_BRANCH and self.training and encoder_out.is_cuda and beside)
         with br:
             if self.ctc_weight != 0.0:
                 loss_ctc = self.ctc(encoder_out, encoder_out_lens, text, text_lengths)
@@ -233,6 +243,14 @@ class ESPnetASRModel(torch.nn.Module):
                     stats[f"cer_interctc_layer{layer_idx}"] = cer_ic
                 n_ic = len(intermediate_outs)
                 loss_ctc = F_.WeightedSumFn.apply(loss_ctc, loss_interctc, 1 - self.interctc_weight, self.interctc_weight / n_ic)
+        if self.use_transducer_decoder:      # espnet_model.py:306-328: the transducer branch takes the attention decoder's place
+            loss_transducer = self._calc_transducer_loss(encoder_out, encoder_out_lens, text, text_lengths)
+            br.join()
+            loss = loss_transducer if loss_ctc is None else F_.WeightedSumFn.apply(loss_transducer, loss_ctc, 1.0, self.ctc_weight)
+            # (espnet's ErrorCalculatorTransducer decodes with a beam search at validation: not computed here)
+            stats.update(loss_transducer=loss_transducer.detach(), cer_transducer=None, wer_transducer=None, loss=loss.detach())
+            weight = torch.full((1,), batch_size, dtype=torch.long, device=loss.device)
+            return loss.view(1), stats, weight
         loss_att, dec_stats = self._decoder_branch(encoder_out, encoder_out_lens, text, text_lengths, **kwargs)
         br.join()
         if self.ctc_weight == 0.0:
@@ -260,6 +278,20 @@ class ESPnetASRModel(torch.nn.Module):
                 cer_att, wer_att = self.error_calculator(ids.cpu(), text.cpu())
         return loss_att, {"loss_att": loss_att.detach() if loss_att is not None else None, "acc": acc_att, "cer": cer_att,
                           "wer": wer_att}
+
+    # espnet_model.py:595-641 over espnet2 asr_transducer/utils.py get_transducer_task_io: decoder input [blank] + labels padded
+    # with blank, int32 targets, t_len, u_len - built on the device (tavsr_lm_shift: x = [blank] + labels, 0 = blank behind them)
+    def _calc_transducer_loss(self, encoder_out, encoder_out_lens, text, text_lengths):
+        if self.blank_id != 0:
+            raise ValueError("the transducer branch takes <blank> at id 0 (the embedding's padding row and the label padding)")
+        u_len = text_lengths.to(torch.int64).contiguous()
+        decoder_in, target, _, _ = ops.lm_shift(text.contiguous(), u_len, self.blank_id)
+        target = target[:, : text.shape[1]].to(torch.int32)
+        t_len = encoder_out_lens.to(torch.int64).contiguous()
+        self.decoder.set_device(encoder_out.device)
+        decoder_out = self.decoder(decoder_in)
+        return F_.grad_apply(RNNTLossFn, encoder_out, decoder_out, t_len, u_len, target, dict(blank=self.blank_id),
+                             *self.joint_network.params())
 
     @torch.no_grad()
     def ctc_greedy(self, speech, speech_lengths):

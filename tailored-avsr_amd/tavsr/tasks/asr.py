@@ -5,7 +5,9 @@ from __future__ import annotations
 import argparse
 
 from ..ctc.ctc import CTC
+from ..decoder.joint_network import JointNetwork
 from ..decoder.mlm_decoder import MLMDecoder
+from ..decoder.transducer_decoder import TransducerDecoder
 from ..decoder.transformer_decoder import TransformerDecoder
 from ..encoder.branchformer.encoder import MyBranchformerEncoder
 from ..frontend.conv3d_resnet18 import Conv3dResNet18
@@ -18,7 +20,7 @@ from ..utils.tokens import load_token_list
 frontend_choices = {"default": DefaultFrontend, "conv3dresnet18": Conv3dResNet18}      # src/tasks/asr.py:93-103
 specaug_choices = {"specaug": SpecAug}
 encoder_choices = {"branchformer": MyBranchformerEncoder}
-decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder}
+decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder, "transducer": TransducerDecoder}
 normalize_choices = {"utterance_mvn": UtteranceMVN}
 model_choices = {"espnet": ESPnetASRModel, "maskctc": MaskCTCModel}
 
@@ -27,6 +29,19 @@ def _pick(table, name, what):
     if name not in table:
         raise ValueError(f"--{what} must be one of {tuple(table)}: {name}")
     return table[name]
+
+
+def build_decoder(args, choices, vocab_size, encoder, encoder_output_size):
+    """-> (decoder, joint_network): src/tasks/asr.py:556-581 == src/tasks/avsr.py:654-680.  ``decoder: transducer`` takes the
+    vocabulary size and ``embed_pad=0`` and comes with a joint network built from ``joint_net_conf``."""
+    if getattr(args, "decoder", None) is None:
+        return None, None
+    decoder_class = _pick(choices, args.decoder, "decoder")
+    if args.decoder == "transducer":
+        decoder = decoder_class(vocab_size, embed_pad=0, **args.decoder_conf)
+        joint = JointNetwork(vocab_size, encoder.output_size(), decoder.dunits, **(getattr(args, "joint_net_conf", None) or {}))
+        return decoder, joint
+    return decoder_class(vocab_size=vocab_size, encoder_output_size=encoder_output_size, **args.decoder_conf), None
 
 
 class ASRTask:
@@ -48,15 +63,12 @@ class ASRTask:
         if getattr(args, "normalize", None) is not None:
             normalize = _pick(normalize_choices, args.normalize, "normalize")(**(args.normalize_conf or {}))
         encoder = _pick(encoder_choices, args.encoder, "encoder")(input_size=input_size, **args.encoder_conf)
-        decoder = None
-        if getattr(args, "decoder", None) is not None:
-            decoder = _pick(decoder_choices, args.decoder, "decoder")(
-                vocab_size=vocab_size, encoder_output_size=encoder.output_size(), **args.decoder_conf)
+        decoder, joint_network = build_decoder(args, decoder_choices, vocab_size, encoder, encoder.output_size())
         ctc = CTC(odim=vocab_size, encoder_output_size=encoder.output_size(), **args.ctc_conf)
         model_class = model_choices.get(getattr(args, "model", "espnet"), ESPnetASRModel)
         model = model_class(vocab_size=vocab_size, frontend=frontend, specaug=specaug, normalize=normalize,
                             preencoder=None, encoder=encoder, postencoder=None, decoder=decoder, ctc=ctc,
-                            joint_network=None, token_list=token_list, **args.model_conf)
+                            joint_network=joint_network, token_list=token_list, **args.model_conf)
         if getattr(args, "init", None) is not None:
             raise NotImplementedError("init: null in every shipped config")
         return model

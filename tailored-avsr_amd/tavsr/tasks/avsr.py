@@ -7,6 +7,7 @@ import argparse
 from ..audiovisual_fusion.adaptive_audiovisual_fusion import AdaptiveAudioVisualFusion
 from ..ctc.ctc import CTC
 from ..decoder.mlm_decoder import MLMDecoder
+from ..decoder.transducer_decoder import TransducerDecoder
 from ..decoder.transformer_decoder import TransformerDecoder
 from ..embedding_for_avsr.default import DefaultEmbeddingLayerForAVSR
 from ..encoder.audiovisual.conventional.encoder import ConventionalEncoder
@@ -18,7 +19,7 @@ from ..models.avsr_maskctc_model import AVSRMaskCTCModel
 from ..models.espnet_model import UtteranceMVN
 from ..specaug.specaug import SpecAug
 from ..utils.tokens import load_token_list
-from .asr import _pick
+from .asr import _pick, build_decoder
 
 visual_frontend_choices = {"conv3dresnet18": Conv3dResNet18}
 acoustic_frontend_choices = {"default": DefaultFrontend}
@@ -27,7 +28,7 @@ acoustic_embed_choices = {"default": DefaultEmbeddingLayerForAVSR}
 visual_embed_choices = {"default": DefaultEmbeddingLayerForAVSR}
 encoder_choices = {"tailored": TailoredEncoder, "conventional": ConventionalEncoder}
 audiovisual_fusion_choices = {"adaptive": AdaptiveAudioVisualFusion}
-decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder}
+decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder, "transducer": TransducerDecoder}
 normalize_choices = {"utterance_mvn": UtteranceMVN}
 model_choices = {"espnet": ESPnetAVSRModel, "maskctc": AVSRMaskCTCModel}
 
@@ -75,16 +76,13 @@ class AVSRTask:
         fusion = _pick(audiovisual_fusion_choices, args.audiovisual_fusion, "audiovisual_fusion")(
             input_size=encoder.output_size(), **args.audiovisual_fusion_conf)
         encoder_output_size = fusion.output_size()
-        decoder = None
-        if getattr(args, "decoder", None) is not None:
-            decoder = _pick(decoder_choices, args.decoder, "decoder")(
-                vocab_size=vocab_size, encoder_output_size=encoder_output_size, **args.decoder_conf)
+        decoder, joint_network = build_decoder(args, decoder_choices, vocab_size, encoder, encoder_output_size)
         ctc = CTC(odim=vocab_size, encoder_output_size=encoder_output_size, **args.ctc_conf)
         model_class = model_choices.get(getattr(args, "model", "espnet"), ESPnetAVSRModel)
         model = model_class(vocab_size=vocab_size, token_list=token_list, specaug=specaug, normalize=normalize,
                             acoustic_frontend=acoustic_frontend, visual_frontend=visual_frontend, acoustic_preencoder=None,
                             visual_preencoder=None, acoustic_embed=acoustic_embed, visual_embed=visual_embed, encoder=encoder,
-                            audiovisual_fusion=fusion, postencoder=None, decoder=decoder, ctc=ctc, joint_network=None,
+                            audiovisual_fusion=fusion, postencoder=None, decoder=decoder, ctc=ctc, joint_network=joint_network,
                             **args.model_conf)
         if getattr(args, "init", None) is not None:
             raise NotImplementedError("init: null in every shipped config")
