@@ -832,6 +832,63 @@ int tavsr_rnnt_greedy_pick(const float* logits, int64_t ldv, const int64_t* tlen
                            int32_t B, int32_t V, tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Transducer beam searches (espnet2 asr/transducer/beam_search_transducer.py align_length_sync_decoding and time_sync_decoding)
+ * for a ragged batch.  csrc/rnnt_search.hip.  kind 0: ALSD, 1: TSD.  U utterances, K = beam rows each, N = U K rows; blank = 0.
+ * One step is a chain of launches with no host read (capturable): lin_dec of the rows' top h (tavsr_gemm), rnnt_search_z,
+ * lin_out (tavsr_gemm), rnnt_row_topk, rnnt_alsd_step / rnnt_tsd_step, rnnt_gather_state and tavsr_lstm_step per layer.
+ *   ws int32 [U][tavsr_rnnt_search_ws(kind, K, T, u_max, max_sym_exp)]: per utterance a 16-word header (0: ALSD's i / TSD's
+ *       frame, 1: beam members, 2: trie nodes, 3: entries of the list, 4: overflow flag - never set inside the bounds below), the
+ *       beam, the trie of every prefix that entered a beam (parent, token per node; node 0 is (blank,); at most 1 + K (T +
+ *       min(u_max, T - 1)) nodes for ALSD, 1 + K T (max_sym_exp - 1) for TSD) with its open-addressing table keyed by (parent node,
+ *       token) - equal prefixes have ONE node, so prefix identity is exact - and a list of (node, score): ALSD's `final` (K (T +
+ *       min(u_max, T - 1)) entries), TSD's A (K max_sym_exp).  tavsr_rnnt_search_ws_offset(.., which): word offset inside a block of
+ *       0: node [K], 1: score [K] (fp32), 2: len [K] (labels; ALSD only), 3: parent [nodes], 4: token [nodes], 5: list node, 6: list
+ *       score (fp32); 7: the node bound, 8: the list bound.
+ *   tavsr_rnnt_search_ok: 1 when the shape is taken: 1 <= K <= 64, K < V, T >= 1, u_max >= 0, 1 <= max_sym_exp <= 8, a block within
+ *       2^30 words and the step's tables (candidate scores K (K + 1) resp. max(K K, K max_sym_exp), the old and the new beam: 11 K
+ *       words) within one workgroup's 160 KiB of LDS.  The entries return TAVSR_EUNSUPPORTED before any launch otherwise.
+ *   rnnt_search_init : the state before the first step: the beam is [(blank,)] with score 0, row_t [N] = 0 for its row (where the
+ *       utterance has a frame) and -1 for every other row.
+ *   rnnt_search_z    : z[n] = tanh(e[n / K][row_t[n]] + d[n]), e [U][T][J], d [N][J]; a row with row_t[n] < 0 is skipped: z[n] =
+ *       0 and no frame is read.
+ *   rnnt_row_topk    : one workgroup per row of logits [N][ldv]: lp_blank[n] = log_softmax(logits[n][:V])[0], topv / topi [N][K] =
+ *       the K largest log-probabilities of the labels 1 .. V - 1 in descending order with their ids, the lower id first among
+ *       equal values.  A row with row_t[n] < 0 is skipped and its outputs left alone (row_t NULL: every row).
+ *   rnnt_alsd_step   : one value of i per utterance (nothing once i reaches T_u + min(u_max, T_u - 1)): the members with row_t >=
+ *       0 are B_; A = per member its blank extension, then its K label extensions; blank extensions at frame T_u - 1 are appended
+ *       to `final`; B = the K best of A (stable: the earlier entry first among equal scores), recombined (a later equal prefix
+ *       adds its score into the first with logaddexp and disappears).  Per row n of the new beam: parent[n] = the row whose state
+ *       it takes, tok[n] / commit[n] = the label and 1, or 0 and 0 for a blank extension, row_t[n] = its frame at i + 1 (-1: not
+ *       in B_).  Rows that hold no member copy themselves.
+ *   rnnt_tsd_step    : expansion v of the current frame per utterance (nothing once the frame reaches T_u).  The beam rows are C.
+ *       A member of C whose prefix the list A held before this v adds score + lp_blank into that entry with logaddexp; any other
+ *       is appended and a_src [U][K max_sym_exp] names its row at that place (-1 elsewhere).  v < max_sym_exp - 1: C = the K best
+ *       of all label extensions of C (parent / tok / commit = 1 per row, row_t = the frame).  v = max_sym_exp - 1: the beam = the K
+ *       best of A, b_sel[n] = U-wide index u K max_sym_exp + place of the A entry whose state row n takes (-1: none), the frame
+ *       advances, row_t = the next frame.  A is emptied at v = 0.
+ *   rnnt_gather_state: dst_h / dst_c [L][Nd][H] row n = src_h / src_c [L][Ns][H] row idx[n]; idx[n] < 0 leaves the row alone.
+ *       Not in place.  The LSTM step that follows runs tavsr_lstm_step unchanged, so a prefix's state has the same bits in
+ *       whichever row it is computed.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_rnnt_search_ok(int32_t kind, int32_t K, int32_t V, int32_t T, int32_t u_max, int32_t max_sym_exp);
+int64_t tavsr_rnnt_search_ws(int32_t kind, int32_t K, int32_t T, int32_t u_max, int32_t max_sym_exp);
+int32_t tavsr_rnnt_search_ws_offset(int32_t kind, int32_t K, int32_t T, int32_t u_max, int32_t max_sym_exp, int32_t which);
+int tavsr_rnnt_search_init(int32_t* ws, const int64_t* tlens, int32_t* row_t, int32_t U, int32_t kind, int32_t K, int32_t V,
+                           int32_t T, int32_t u_max, int32_t max_sym_exp, tavsr_stream_t stream);
+int tavsr_rnnt_search_z(const float* e, const float* d, const int32_t* row_t, float* z, int32_t N, int32_t K, int32_t T,
+                        int32_t J, tavsr_stream_t stream);
+int tavsr_rnnt_row_topk(const float* logits, int64_t ldv, const int32_t* row_t, float* lp_blank, float* topv, int32_t* topi,
+                        int32_t N, int32_t V, int32_t K, tavsr_stream_t stream);
+int tavsr_rnnt_gather_state(const float* src_h, const float* src_c, const int32_t* idx, float* dst_h, float* dst_c, int32_t L,
+                            int32_t Ns, int32_t Nd, int32_t H, tavsr_stream_t stream);
+int tavsr_rnnt_alsd_step(int32_t* ws, const int64_t* tlens, const float* lp_blank, const float* topv, const int32_t* topi,
+                         int32_t* row_t, int32_t* parent, int64_t* tok, uint8_t* commit, int32_t U, int32_t K, int32_t V,
+                         int32_t T, int32_t u_max, tavsr_stream_t stream);
+int tavsr_rnnt_tsd_step(int32_t* ws, const int64_t* tlens, const float* lp_blank, const float* topv, const int32_t* topi,
+                        int32_t* row_t, int32_t* parent, int64_t* tok, uint8_t* commit, int32_t* a_src, int32_t* b_sel,
+                        int32_t v, int32_t U, int32_t K, int32_t V, int32_t T, int32_t max_sym_exp, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Mask-CTC decoding (src/models/maskctc_model.py:285-349, MaskCTCInference.forward), one workgroup per utterance,
  * no host value read or written (a decode loop is one stream of launches, capturable).  Integer outputs: bit-exact contract.
  *   maskctc_init: from the CTC logits (strides as ctc_greedy): per frame t < hlens[b] the argmax (ctc_greedy's rule) and

@@ -833,7 +833,8 @@ class Speech2Text:
     def __init__(self, asr_model, lm=None, beam_size: int = 20, ctc_weight: float = 0.5, lm_weight: float = 1.0,
                  penalty: float = 0.0, nbest: int = 1, maxlenratio: float = 0.0, minlenratio: float = 0.0,
                  skip_zero_weight: bool = False, timestamps: bool = False, frame_seconds: float = 0.04,
-                 ngram_file: Optional[str] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9, time_sync: bool = False):
+                 ngram_file: Optional[str] = None, ngram_scorer: str = "full", ngram_weight: float = 0.9, time_sync: bool = False,
+                 transducer_conf: Optional[dict] = None):
         # timestamps: every returned hypothesis is aligned to its utterance's CTC posteriors after the search (one launch of
         # tavsr_ctc_align for the whole batch) and its result tuple gains a fifth element, the record of utils/timestamps.py.
         # frame_seconds: one encoder frame - 10 ms hop x 4 subsampling for audio, 25 fps for video: 0.04 s in every shipped recipe.
@@ -846,14 +847,18 @@ class Speech2Text:
         self.lm = None if lm is None else lm.eval()
         self.nbest = nbest
         self.encode = CapturedEncode(self.asr_model)
-        # a transducer model is searched by BeamSearchTransducer (avsr_inference.py:181-207): greedy only, beam_size=1 (inference/transducer.py)
+        # a transducer model is searched by BeamSearchTransducer(beam_size=beam_size, **transducer_conf) (avsr_inference.py:181-207):
+        # greedy with beam_size=1, ALSD or TSD with transducer_conf={"search_type": "alsd" / "tsd"} (inference/transducer.py);
+        # transducer_conf is ignored for every other model, as in the reference
         self.beam_search_transducer = None
         if getattr(asr_model, "use_transducer_decoder", False):
             from .transducer import BeamSearchTransducer
             if lm is not None or ngram_file is not None or time_sync:
-                raise ValueError("the transducer search takes no LM, n-gram file or time_sync (greedy search only: beam_size=1)")
-            self.beam_search_transducer = BeamSearchTransducer(asr_model.decoder, asr_model.joint_network, beam_size, nbest=nbest,
-                                                               token_list=asr_model.token_list)
+                raise ValueError("the transducer searches (greedy, ALSD, TSD) take no LM, n-gram file or time_sync")
+            conf = dict(transducer_conf or {})
+            conf.setdefault("nbest", nbest)
+            self.beam_search_transducer = BeamSearchTransducer(asr_model.decoder, asr_model.joint_network, beam_size,
+                                                               token_list=asr_model.token_list, **conf)
             self.beam_search = self.beam_search_transducer
             return
         # time_sync: espnet's BeamSearchTimeSync in place of the label-synchronous search (avsr_inference.py:257-275;

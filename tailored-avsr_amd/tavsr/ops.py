@@ -2605,3 +2605,100 @@ def rnnt_greedy_pick(logits, tlens, blank, frame, tok, commit, hyp, hyp_len, sco
     assert commit.dtype == torch.uint8 and hyp.dtype == torch.int64 and hyp.is_contiguous() and hyp_len.dtype == torch.int32
     check(lib().tavsr_rnnt_greedy_pick(ptr(logits), logits.stride(0), ptr(tlens), int(blank), ptr(frame), ptr(tok), ptr(commit), ptr(hyp),
                                        hyp.shape[1], ptr(hyp_len), ptr(score), B, V, stream()), "tavsr_rnnt_greedy_pick")
+
+
+# ---------------------------------------------------------------------------------------------- transducer beam searches (csrc/rnnt_search.hip)
+RNNT_SEARCH_KINDS = {"alsd": 0, "tsd": 1}
+RNNT_SEARCH_LIMIT = ("1 <= beam <= 64, beam < vocabulary, at least one frame, u_max >= 0, 1 <= max_sym_exp <= 8, the trie of an "
+                     "utterance within 2^30 words")
+
+
+def rnnt_search_ok(kind, K, V, T, u_max=50, max_sym_exp=2) -> bool:
+    """does the transducer beam search ``kind`` ("alsd" / "tsd") take this shape?  The library's answer (include/tavsr.h)."""
+    return bool(lib().tavsr_rnnt_search_ok(RNNT_SEARCH_KINDS[kind], int(K), int(V), int(T), int(u_max), int(max_sym_exp)))
+
+
+def rnnt_search_ws(kind, K, V, T, u_max=50, max_sym_exp=2):
+    """(int32 words of an utterance's block, {name: word offset or bound}) of ``tavsr_rnnt_search_*``; ValueError where the shape
+    is not taken, before anything is launched"""
+    if not rnnt_search_ok(kind, K, V, T, u_max, max_sym_exp):
+        raise ValueError(f"transducer {kind} search: beam {K}, {V} tokens, {T} frames, u_max {u_max}, max_sym_exp {max_sym_exp} is not "
+                         f"supported (tavsr_rnnt_search_ok): {RNNT_SEARCH_LIMIT}")
+    args = (RNNT_SEARCH_KINDS[kind], int(K), int(T), int(u_max), int(max_sym_exp))
+    names = ("node", "score", "len", "parent", "token", "list_node", "list_score", "nodes", "list")
+    return int(lib().tavsr_rnnt_search_ws(*args)), {n: int(lib().tavsr_rnnt_search_ws_offset(*args, i)) for i, n in enumerate(names)}
+
+
+def _i32(*tensors):
+    require_cuda(*tensors)
+    assert all(t.dtype == torch.int32 and t.is_contiguous() for t in tensors)
+
+
+def rnnt_search_init(kind, ws, tlens, row_t, K, V, T, u_max=50, max_sym_exp=2):
+    """the state before the first step of every utterance (tavsr_rnnt_search_init)"""
+    _i32(ws, row_t)
+    U = ws.shape[0]
+    assert tlens.dtype == torch.int64 and tlens.is_cuda and tlens.shape == (U,) and row_t.numel() == U * K
+    check(lib().tavsr_rnnt_search_init(ptr(ws), ptr(tlens), ptr(row_t), U, RNNT_SEARCH_KINDS[kind], int(K), int(V), int(T), int(u_max),
+                                       int(max_sym_exp), stream()), "tavsr_rnnt_search_init")
+
+
+def rnnt_search_z(e, d, row_t, K, out=None):
+    """z [N, J] = tanh(e[n // K, row_t[n]] + d[n]); rows with row_t < 0 are 0 (tavsr_rnnt_search_z)"""
+    U, T, J = e.shape
+    _i32(row_t)
+    require_cuda(e, d)
+    assert e.is_contiguous() and d.is_contiguous() and d.shape == (U * K, J) and row_t.numel() == U * K
+    out = empty(U * K, J, like=e) if out is None else out
+    check(lib().tavsr_rnnt_search_z(ptr(e), ptr(d), ptr(row_t), ptr(out), U * K, int(K), T, J, stream()), "tavsr_rnnt_search_z")
+    return out
+
+
+def rnnt_row_topk(logits, K, row_t=None, out=None):
+    """logits [N, V] -> (lp_blank [N], topv [N, K], topi int32 [N, K]): the log-softmax's blank and its K best labels, the lower
+    id first among equals; rows with row_t < 0 are left alone (tavsr_rnnt_row_topk)"""
+    N, V = logits.shape
+    require_cuda(logits, row_t)
+    assert logits.stride(1) == 1 and logits.dtype == f32 and (row_t is None or (row_t.dtype == torch.int32 and row_t.numel() == N))
+    lpb, topv, topi = (empty(N, like=logits), empty(N, K, like=logits), torch.empty((N, K), dtype=torch.int32, device=logits.device)) \
+        if out is None else out
+    check(lib().tavsr_rnnt_row_topk(ptr(logits), logits.stride(0), ptr(row_t), ptr(lpb), ptr(topv), ptr(topi), N, V, int(K), stream()),
+          "tavsr_rnnt_row_topk")
+    return lpb, topv, topi
+
+
+def rnnt_gather_state(src, idx, dst):
+    """dst (h, c) [L, Nd, H] row n = src (h, c) [L, Ns, H] row idx[n]; idx[n] < 0 leaves the row alone (tavsr_rnnt_gather_state)"""
+    (sh, sc), (dh, dc) = src, dst
+    _i32(idx)
+    require_cuda(sh, sc, dh, dc)
+    Ln, Ns, H = sh.shape
+    Nd = dh.shape[1]
+    assert all(t.is_contiguous() and t.dtype == f32 for t in (sh, sc, dh, dc)) and sc.shape == sh.shape and dc.shape == dh.shape
+    assert dh.shape == (Ln, Nd, H) and idx.numel() == Nd
+    check(lib().tavsr_rnnt_gather_state(ptr(sh), ptr(sc), ptr(idx), ptr(dh), ptr(dc), Ln, Ns, Nd, H, stream()), "tavsr_rnnt_gather_state")
+
+
+def _rnnt_step_check(ws, tlens, lpb, topv, topi, row_t, parent, tok, commit):
+    _i32(ws, topi, row_t, parent)
+    require_cuda(tlens, lpb, topv, tok, commit)
+    U, (N, K) = ws.shape[0], topv.shape
+    assert N == U * K and tlens.dtype == torch.int64 and tok.dtype == torch.int64 and commit.dtype == torch.uint8
+    assert lpb.is_contiguous() and topv.is_contiguous() and all(t.numel() == N for t in (lpb, row_t, parent, tok, commit))
+    return U, K
+
+
+def rnnt_alsd_step(ws, tlens, lpb, topv, topi, row_t, parent, tok, commit, V, T, u_max):
+    """one value of i of ALSD for every utterance (tavsr_rnnt_alsd_step); ws, row_t, parent, tok, commit are updated in place"""
+    U, K = _rnnt_step_check(ws, tlens, lpb, topv, topi, row_t, parent, tok, commit)
+    check(lib().tavsr_rnnt_alsd_step(ptr(ws), ptr(tlens), ptr(lpb), ptr(topv), ptr(topi), ptr(row_t), ptr(parent), ptr(tok), ptr(commit),
+                                     U, K, int(V), int(T), int(u_max), stream()), "tavsr_rnnt_alsd_step")
+
+
+def rnnt_tsd_step(ws, tlens, lpb, topv, topi, row_t, parent, tok, commit, a_src, b_sel, v, V, T, max_sym_exp):
+    """expansion ``v`` of the current frame of TSD for every utterance (tavsr_rnnt_tsd_step)"""
+    U, K = _rnnt_step_check(ws, tlens, lpb, topv, topi, row_t, parent, tok, commit)
+    _i32(a_src, b_sel)
+    assert a_src.numel() == U * K * max_sym_exp and b_sel.numel() == U * K
+    check(lib().tavsr_rnnt_tsd_step(ptr(ws), ptr(tlens), ptr(lpb), ptr(topv), ptr(topi), ptr(row_t), ptr(parent), ptr(tok), ptr(commit),
+                                    ptr(a_src), ptr(b_sel), int(v), U, K, int(V), int(T), int(max_sym_exp), stream()), "tavsr_rnnt_tsd_step")
