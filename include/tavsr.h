@@ -498,6 +498,26 @@ int tavsr_dwconv_gate_bwd_act(const float* du, const float* gn, const float* r, 
                               tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * E-Branchformer's merge convolution (csrc/dwconv_add.hip; espnet2 e_branchformer_encoder.py, EBranchformerEncoderLayer:
+ * x_concat + depthwise_conv_fusion(x_concat)), a depthwise 1-D convolution over time with its own input added back:
+ *   u[b,t,c] = x[b,t,c] + bias[c] + sum_j w[c,j] * x[b, t + j - (K-1)/2, c]      (terms outside 0 <= t < T are zero)
+ * x: [B*T][ldx], u: [B*T][ldu] (ldx, ldu >= C), w: [C][K] (torch [C,1,K]), bias: [C].  T is dense: the kernel knows no lengths.
+ * bwd, from du [B*T][lddu]:  dx [B*T][lddx] = du + the correlation of du with the flipped taps,
+ *   dw[c,j] = sum_{b,t} du[b,t,c] x[b,t+j-(K-1)/2,c],  dbias[c] = sum_{b,t} du[b,t,c]   (accumulate != 0: added to dw / dbias).
+ * dw and dbias are reduced in a fixed order (per-block partial slabs in ws, then tavsr_sum_partials): no float atomics, the
+ * same bits every run.  ws >= tavsr_dwconv_add_bwd_ws(B, T, C, K) floats.
+ * tavsr_dwconv_add_ok: 1 for K odd, 1 <= K <= 31 and 1 <= B <= 65535, T >= 1, C >= 1 with B * T < 2^31; where it is 0 the
+ * entries return TAVSR_EUNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_dwconv_add_ok(int32_t B, int32_t T, int32_t C, int32_t K);
+int tavsr_dwconv_add_fwd(const float* x, int64_t ldx, const float* w, const float* bias, float* u, int64_t ldu,
+                         int32_t B, int32_t T, int32_t C, int32_t K, tavsr_stream_t stream);
+int64_t tavsr_dwconv_add_bwd_ws(int32_t B, int32_t T, int32_t C, int32_t K);
+int tavsr_dwconv_add_bwd(const float* du, int64_t lddu, const float* x, int64_t ldx, const float* w, float* dx, int64_t lddx,
+                         float* dw, float* dbias, int32_t accumulate, float* ws, int32_t B, int32_t T, int32_t C, int32_t K,
+                         tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The tailored audio-visual encoder layer (csrc/layer.hip): TailoredEncoderLayer.forward
  * (src/encoder/audiovisual/tailored/encoder_layer.py:118-274).  Each modality stream runs  macaron FFN -> ONE branch (rel-pos
  * attention or cgMLP, per layer and modality: encoder.py's acoustic_use_attn / visual_use_attn lists) with its residual -> FFN ->

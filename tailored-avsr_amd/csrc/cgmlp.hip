@@ -473,6 +473,13 @@ __global__ void dwconv_split_kernel(const float* __restrict__ sum, float* __rest
   else db[c] = accumulate ? db[c] + v : v;
 }
 
+int dwconv_split(const float* sum, float* dw, float* dbias, int C, int K, int accumulate, hipStream_t stream) {
+  const int n = C * (K + 1);
+  hipLaunchKernelGGL(dwconv_split_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, sum, dw, dbias, C, K, accumulate);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
 // ------------------------------- learned_ave merge ---------------------------------------------
 // One 512-thread block per utterance b: waves 0-3 work on branch 1, waves 4-7 on branch 2, in lock step.
 // For branch k in {1,2}:
@@ -1045,9 +1052,7 @@ static int dwconv_gate_bwd_impl(const float* du, const float* gn, const float* r
   float* sum = ws + (int64_t)nblk * n;
   int rc = tavsr_sum_partials(ws, nblk, n, sum, n, 0, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(dwconv_split_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, sum, dw, dbias, C, K, accumulate);
-  TAVSR_LAUNCH_CHECK();
-  return TAVSR_OK;
+  return dwconv_split(sum, dw, dbias, C, K, accumulate, s);
 }
 
 extern "C" int tavsr_dwconv_gate_bwd(const float* du, const float* gn, const float* r, int64_t ldr, const float* conv,

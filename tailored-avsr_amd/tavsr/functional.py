@@ -96,6 +96,13 @@ DESC_FIELD = {n: f for n, f, _ in _BF_PARAMS if f is not None}                 #
 _DESC_PARAMS = tuple((f, n) for n, f, _ in _BF_PARAMS if f is not None)
 _BWD_FIELDS = tuple((g, n) for n, _, g in _BF_PARAMS if g is not None)          # gradient slot -> parameter
 _I = {n: i for i, n in enumerate(BF_PARAM_NAMES)}
+# ... of an E-Branchformer layer (merge ``dwconv``): the same list with the merge convolution's two parameters behind it.  A list of
+# its own: a Branchformer layer gathered by it would carry two ``None`` entries, and the C-side backward takes complete lists only.
+EBF_PARAM_NAMES = BF_PARAM_NAMES + ("depthwise_conv_fusion.weight", "depthwise_conv_fusion.bias")
+
+
+def _param_names(cfg):
+    return EBF_PARAM_NAMES if cfg["merge"] == "dwconv" else BF_PARAM_NAMES
 
 
 def _layer_c_ok(x, cfg, P, pd, pos_emb=None) -> bool:
@@ -392,6 +399,11 @@ def _bf_merge_fwd(p, cfg, xa, xm, cat, x1, mp, rowdots, lens, B, T, need):
         m = ops.axpby(xa, xm, 1.0 - cw, cw)
     elif xa is not None and xm is not None and merge == "concat":
         m = cat
+    elif xa is not None and xm is not None and merge == "dwconv":
+        # E-Branchformer (espnet2 e_branchformer_encoder.py): merge_proj(cat + depthwise_conv_fusion(cat)); the sum is kept - it is
+        # merge_proj's input, which its weight gradient reads - and so is cat, which the convolution's weight gradient reads
+        cw = p["depthwise_conv_fusion.weight"]
+        m = ops.dwconv_add_fwd(cat, cw.reshape(cw.shape[0], -1), p["depthwise_conv_fusion.bias"], B, T)
     else:
         m = xa if xa is not None else xm
     if x2 is not None:
@@ -433,6 +445,13 @@ def _bf_merge_bwd(p, cfg, sv, dx2, dxd, lens, B, T, grp, G):
         D = dx2.shape[1]
         _drop_bwd_(dm, ms.t_cat)
         return dm[:, :D], dm[:, D:], False
+    if two and merge == "dwconv":      # dm is the gradient of cat + conv(cat): through the convolution, then as concat
+        D = dx2.shape[1]
+        cw = p["depthwise_conv_fusion.weight"]
+        dm, gcw, G["depthwise_conv_fusion.bias"] = ops.dwconv_add_bwd(dm, sv["cat"], cw.reshape(cw.shape[0], -1), B, T)
+        G["depthwise_conv_fusion.weight"] = gcw.view_as(cw)
+        _drop_bwd_(dm, ms.t_cat)
+        return dm[:, :D], dm[:, D:], False
     return (dm if has_attn else None), (dm if has_mlp else None), False
 
 
@@ -448,7 +467,7 @@ class BranchformerLayerFn(torch.autograd.Function):
             return _layer_c_forward(ctx, x, pos_emb, lens, cfg, P, need)
         B, T, D = x.shape
         M = B * T
-        p = dict(zip(BF_PARAM_NAMES, P))
+        p = dict(zip(_param_names(cfg), P))
         act, merge = cfg["ffn_act"], cfg["merge"]             # learned_ave | fixed_ave | concat (+ identity flag for one branch)
         has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
         two = has_attn and has_mlp
@@ -456,8 +475,16 @@ class BranchformerLayerFn(torch.autograd.Function):
         # the macaron block's finishing launch also normalises its output for the two branches (one statistics pass)
         br_norms = ([(p["norm_mha.weight"], p["norm_mha.bias"])] if has_attn else []) + \
                    ([(p["norm_mlp.weight"], p["norm_mlp.bias"])] if has_mlp else [])
-        x1, sv["ffm"], nbr, bmean, brstd = _FFN.fwd_ln(x.reshape(M, D), *[p[k] for k in FFM_PARAMS], act, 0.5, br_norms, p=pd, save=need)
-        cat = ops.empty(M, 2 * D, like=x) if merge == "concat" else None
+        ffs = cfg.get("ff_scale", 0.5)                        # 1.0 for an E-Branchformer layer without the macaron block
+        if p["feed_forward_macaron.w_1.weight"] is not None:
+            x1, sv["ffm"], nbr, bmean, brstd = _FFN.fwd_ln(x.reshape(M, D), *[p[k] for k in FFM_PARAMS], act, ffs, br_norms, p=pd,
+                                                           save=need)
+        else:      # (E-Branchformer, macaron_ffn=False) the branch LayerNorms are launches of their own
+            x1, sv["ffm"], nbr, bmean, brstd = x.reshape(M, D), None, [], None, None
+            for gam, bet in br_norms:
+                n_, bmean, brstd = ops.layernorm_fwd(x1, gam, bet, EPS_ESPNET)
+                nbr.append(n_)
+        cat = ops.empty(M, 2 * D, like=x) if merge in ("concat", "dwconv") else None
         mp = [p[k] for k in MERGE_PARAMS] if two and merge == "learned_ave" else None
         # the fused tail takes the merge's row dots from the epilogues of the launches that store the branch outputs
         use_rd = (mp is not None and ops.MERGE_ROWDOT and not cfg["merge_identity"] and ops.MERGE_PROJ and ops.MERGE_ROWS
@@ -478,10 +505,14 @@ class BranchformerLayerFn(torch.autograd.Function):
         br.join()
         x2, sv["merge"] = _bf_merge_fwd(p, cfg, xa, xm, cat, x1, mp, (rd_a, rd_m) if rd_a is not None and rd_m is not None else None,
                                         lens, B, T, need)
-        x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, *[p[k] for k in FF_PARAMS], act, 0.5,
-                                                       [(p["norm_final.weight"], p["norm_final.bias"])], p=pd, save=need)
+        if p["feed_forward.w_1.weight"] is not None:
+            x3, sv["ff"], (y,), fmean, frstd = _FFN.fwd_ln(x2, *[p[k] for k in FF_PARAMS], act, ffs,
+                                                           [(p["norm_final.weight"], p["norm_final.bias"])], p=pd, save=need)
+        else:      # (E-Branchformer, use_ffn=False) norm_final is a LayerNorm of its own
+            x3, sv["ff"] = x2, None
+            y, fmean, frstd = ops.layernorm_fwd(x2, p["norm_final.weight"], p["norm_final.bias"], EPS_ESPNET)
         sv["final"] = (x3, fmean, frstd)
-        sv["x1"], sv["xa"], sv["xm"] = x1, xa, xm
+        sv["x1"], sv["xa"], sv["xm"], sv["cat"] = x1, xa, xm, (cat if merge == "dwconv" else None)
         ctx.sv, ctx.cfg, ctx.P, ctx.lens, ctx.pos_emb = sv, cfg, P, lens, pos_emb
         ctx.shape = (B, T, D)
         cfg["_last_w"] = sv["merge"].wts   # (weight_global, weight_local) for the introspection attributes
@@ -497,20 +528,25 @@ class BranchformerLayerFn(torch.autograd.Function):
         B, T, D = ctx.shape
         act = cfg["ffn_act"]
         has_attn, has_mlp = cfg["has_attn"], cfg["has_mlp"]
-        p = dict(zip(BF_PARAM_NAMES, P))
+        p = dict(zip(_param_names(cfg), P))
         G = {}
         beside = ops.wgrad_may_go_beside(P)
         grp = ops.WgradGroup()     # every weight gradient of the layer in one grouped launch (flushed at the end)
         lng = ops.LNGroup()        # ... and the five d=256 LayerNorms' (dgamma, dbeta) partials in one reduction
         x3, fmean, frstd = sv["final"]
         # each LayerNorm backward whose dx the next block's dropout mask is applied to also writes the masked copy
-        t_ffm = sv["ffm"].t_out
-        dx3, G["norm_final.weight"], G["norm_final.bias"], *dyd = lng.bwd(dy.contiguous().view(B * T, D), x3, fmean, frstd,
-                                                                         p["norm_final.weight"], drop=sv["ff"].t_out)
-        dx2, gs, *dxd = _FFN.bwd(dx3, sv["ff"], p["norm_ff.weight"], p["feed_forward.w_1.weight"], p["feed_forward.w_2.weight"], act, 0.5,
-                                 grp=grp, lng=lng, dyd=dyd[0] if dyd else None,
-                                 out_drop=None if cfg["merge_identity"] else sv["merge"].t_m)
-        G.update(zip(FF_PARAMS, gs))
+        ffs = cfg.get("ff_scale", 0.5)
+        t_ffm = sv["ffm"].t_out if sv["ffm"] is not None else None
+        t_m = None if cfg["merge_identity"] else sv["merge"].t_m
+        if sv["ff"] is not None:
+            dx3, G["norm_final.weight"], G["norm_final.bias"], *dyd = lng.bwd(dy.contiguous().view(B * T, D), x3, fmean, frstd,
+                                                                             p["norm_final.weight"], drop=sv["ff"].t_out)
+            dx2, gs, *dxd = _FFN.bwd(dx3, sv["ff"], p["norm_ff.weight"], p["feed_forward.w_1.weight"], p["feed_forward.w_2.weight"], act,
+                                     ffs, grp=grp, lng=lng, dyd=dyd[0] if dyd else None, out_drop=t_m)
+            G.update(zip(FF_PARAMS, gs))
+        else:      # no closing feed-forward block: norm_final's backward hands the merge its gradient (and the masked copy)
+            dx2, G["norm_final.weight"], G["norm_final.bias"], *dxd = lng.bwd(dy.contiguous().view(B * T, D), x3, fmean, frstd,
+                                                                             p["norm_final.weight"], drop=t_m)
         dxa, dxm, masked = _bf_merge_bwd(p, cfg, sv, dx2, dxd[0] if dxd else None, ctx.lens, B, T, grp, G)
         x1 = sv["x1"]
         dx1 = dx2  # residual path; branch gradients are folded in through dx_add
@@ -534,16 +570,19 @@ class BranchformerLayerFn(torch.autograd.Function):
         if has_attn:     # same accumulation order into dx1 as a single stream: cgMLP branch first, then attention
             dx1, G["norm_mha.weight"], G["norm_mha.bias"], *dyd = lng.bwd(dn_a, x1, sa.mean, sa.rstd, p["norm_mha.weight"], dx_add=dx1,
                                                                           drop=t_ffm)
-        dx, gs = _FFN.bwd(dx1, sv["ffm"], p["norm_ff_macaron.weight"], p["feed_forward_macaron.w_1.weight"],
-                          p["feed_forward_macaron.w_2.weight"], act, 0.5, grp=grp, lng=lng, dyd=dyd[0] if dyd else None)
-        G.update(zip(FFM_PARAMS, gs))
+        if sv["ffm"] is not None:
+            dx, gs = _FFN.bwd(dx1, sv["ffm"], p["norm_ff_macaron.weight"], p["feed_forward_macaron.w_1.weight"],
+                              p["feed_forward_macaron.w_2.weight"], act, ffs, grp=grp, lng=lng, dyd=dyd[0] if dyd else None)
+            G.update(zip(FFM_PARAMS, gs))
+        else:
+            dx = dx1
         if beside:       # no reader before the end of the pass: beside the next layer's chain (the positional chain first)
             ops.wgrad_beside(lambda: ([f() for f in late], grp.flush(), lng.flush()))
         else:
             grp.flush()
             lng.flush()
         ctx.sv = None
-        return (dx.view(B, T, D), None, None, None, *[None if prm is None else G.get(n) for n, prm in zip(BF_PARAM_NAMES, P)])
+        return (dx.view(B, T, D), None, None, None, *[None if prm is None else G.get(n) for n, prm in zip(_param_names(cfg), P)])
 
 
 # ------------------------------------------------------------------------------------------------

@@ -1168,6 +1168,38 @@ def dwconv_gate_bwd(du, gn, r, conv, w, dr, B, T, zr=None, act="gelu"):
     return dgn, dw, db
 
 
+def dwconv_add_ok(B, T, Cn, K) -> bool:
+    return bool(lib().tavsr_dwconv_add_ok(B, T, Cn, K))
+
+
+def dwconv_add_fwd(x, w, bias, B, T, out=None):
+    """u = x + depthwise_conv1d_K(x) over time (E-Branchformer's merge convolution): x [B*T, C] rows (any row stride),
+    w [C, K], bias [C].  T is dense: no lengths.  Shapes the kernel does not take are an error (there is no other route)."""
+    M, Cn = x.shape
+    require_cuda(x, w, bias)
+    assert M == B * T and x.stride(1) == 1 and w.is_contiguous()
+    if out is None:
+        out = empty(M, Cn, like=x)
+    check(lib().tavsr_dwconv_add_fwd(ptr(x), x.stride(0), ptr(w), ptr(bias), ptr(out), out.stride(0), B, T, Cn, w.shape[-1], stream()),
+          "tavsr_dwconv_add_fwd")
+    return out
+
+
+def dwconv_add_bwd(du, x, w, B, T, dx=None):
+    """backward of dwconv_add_fwd -> (dx, dw [C, K], dbias [C]); dw / dbias are reduced in a fixed order (no atomics)."""
+    M, Cn = x.shape
+    K = w.shape[-1]
+    require_cuda(du, x, w)
+    assert M == B * T and du.shape == x.shape and du.stride(1) == 1 and x.stride(1) == 1 and w.is_contiguous()
+    if dx is None:
+        dx = empty(M, Cn, like=x)
+    dw, db = empty(Cn, K, like=x), empty(Cn, like=x)
+    ws = empty(max(1, lib().tavsr_dwconv_add_bwd_ws(B, T, Cn, K)), like=x)
+    check(lib().tavsr_dwconv_add_bwd(ptr(du), du.stride(0), ptr(x), x.stride(0), ptr(w), ptr(dx), dx.stride(0), ptr(dw), ptr(db), 0,
+                                     ptr(ws), B, T, Cn, K, stream()), "tavsr_dwconv_add_bwd")
+    return dx, dw, db
+
+
 def _ptr_array(ts: Sequence[torch.Tensor]):
     require_cuda(*ts)
     return (C.c_void_p * len(ts))(*[_addr(t) for t in ts])
