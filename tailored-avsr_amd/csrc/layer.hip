@@ -333,7 +333,7 @@ namespace {
 
 struct WItem { const float* dy; int64_t lddy; const float* x; int64_t ldx; int rows, N, K; float alpha; float *out, *gb; };
 
-struct WGroup {        // tavsr/ops.py:WgradGroup
+struct WGroup {        // tavsr/ops/matmul.py:WgradGroup
   WItem it[16];
   int n = 0;
   void add(const float* dy, int64_t lddy, const float* x, int64_t ldx, int rows, int N, int K, float alpha, float* out, float* gb) {
@@ -403,7 +403,7 @@ struct WGroup {        // tavsr/ops.py:WgradGroup
   }
 };
 
-struct LnGroup {       // tavsr/ops.py:LNGroup for the five d_model LayerNorms of a layer
+struct LnGroup {       // tavsr/ops/norm.py:LNGroup for the five d_model LayerNorms of a layer
   float* slab = nullptr;
   int64_t slab_ld = 0;
   int nb = 0, k = 0, M = 0, D = 0;
@@ -418,7 +418,7 @@ struct LnGroup {       // tavsr/ops.py:LNGroup for the five d_model LayerNorms o
                                               seed, off, (tavsr_stream_t)s);
     return tavsr_layernorm_bwd_partial(dy, D, x, D, mean, rstd, gamma, dx_add, dx_add ? D : 0, dx, D, part, slab_ld, M, D, (tavsr_stream_t)s);
   }
-  // dy as the unsummed partials of tavsr_ffn2_bwd_dx(dn = NULL) (tavsr/ops.py: LNGroup.bwd on ops.DnSlabs)
+  // dy as the unsummed partials of tavsr_ffn2_bwd_dx(dn = NULL) (tavsr/ops/norm.py: LNGroup.bwd on ops.DnSlabs)
   int bwd_slab(const float* slabs, int wpb, int rbr, const float* x, const float* mean, const float* rstd, const float* gamma, const float* dx_add,
                float* dx, float* dx_drop, float p, const uint64_t* seed, uint64_t off, bool dry, hipStream_t s) {
     float* part = dry ? nullptr : slab + (int64_t)k * 2 * D;

@@ -3,7 +3,7 @@
 //                               occupy its queue, so that a missing dependency between two queues becomes deterministic;
 //   tavsr_race_probe(us, mode)  arms the same delay inside the C-side sequencers that fork a second queue themselves
 //                               (tavsr_branchformer_layer_fwd): mode 0 = head of the forked section, 1 = behind the join on the
-//                               calling queue, 2 = alternately per call.  tavsr/ops.py (TAVSR_RACE_PROBE) drives both.
+//                               calling queue, 2 = alternately per call.  tavsr/ops/streams.py (TAVSR_RACE_PROBE) drives both.
 // The reference is single-queue (src/models/espnet_model.py:258-356 runs on torch's current stream): results must not depend on
 // how the launches of one step are spread over queues; tests/test_gpu_streams.py holds that.
 #include "common.h"

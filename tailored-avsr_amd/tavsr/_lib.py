@@ -122,7 +122,7 @@ def lib() -> C.CDLL:
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = restype, argtypes
         us = float(os.environ.get("TAVSR_RACE_PROBE", "0") or 0)
-        if us > 0:      # race amplifier of the C-side sequencers (tests; ops.py arms the Python-side scopes from the same variables)
+        if us > 0:      # race amplifier of the C-side sequencers (tests; ops/streams.py arms the Python-side scopes from the same variables)
             _lib.tavsr_race_probe(us, {"body": 0, "join": 1, "alt": 2}[os.environ.get("TAVSR_RACE_PROBE_MODE", "alt")])
     return _lib
 
@@ -145,15 +145,10 @@ def stream() -> int:
 
 
 # ---------------------------------------------------------------------------------------------- stream safety
-# The package runs independent sections on forked HIP streams (ops.BranchScope; autograd replays a node on the stream its
-# forward ran on).  Two rules make that safe against torch's per-stream caching allocator, and both are enforced HERE, at the
-# one place where a tensor becomes a raw pointer, instead of by hand at the fork sites:
-#   1. a tensor handed to a launch on a forked stream is ``record_stream``-ed on it (a no-op for tensors of that stream's own
-#      pool): the allocator will not hand its block to anybody before the forked stream has passed the point of the free;
-#   2. a forked stream never starts work without first waiting for the stream that owns it (``BranchScope.__enter__``,
-#      ``enter_node`` at the head of every autograd backward): blocks of the forked stream's pool are only re-used behind
-#      every reader the owning stream had enqueued when they were freed.
-# ``tests/test_host_api.py`` checks that no module takes ``.data_ptr()`` behind this file's back.
+# Independent sections run on forked HIP streams (ops.BranchScope).  The two rules that make that safe against torch's per-stream
+# caching allocator are stated at the head of tavsr/ops/streams.py and enforced HERE, at the one place where a tensor becomes a raw
+# pointer (rule 1: ``ptr`` / ``addr`` -> ``_note``) and at the head of every autograd backward (rule 2: ``enter_node``), instead of by
+# hand at the fork sites.
 _FORKED = {}          # raw handle -> (torch.cuda.Stream forked, torch.cuda.Stream owner)
 _CUR_FORK = None      # the forked stream launches currently go to (None: an owning / main stream), kept by the scopes below
 _CUR_SEEN = None      # addresses already recorded in the innermost scope (a scope re-reads its operands many times)

@@ -280,3 +280,50 @@ def test_weight_gradient_group_deals_many_layers_problems_into_launches_of_one_r
     assert [p[0].shape[0] for c in chunks for p in c] == sorted((p[0].shape[0] for p in items), reverse=True)     # longest reductions first
     small = layer[:10]
     assert WgradGroup._chunks(small) == [small] and WgradGroup._chunks([]) == []
+
+
+def _ops_submodules():
+    import importlib
+    import pkgutil
+    from tavsr import ops
+    return ops, [importlib.import_module(f"tavsr.ops.{m.name}") for m in pkgutil.iter_modules(ops.__path__)]
+
+
+def test_ops_switches_have_one_definition_that_every_family_reads():
+    """the route switches and limits of ``tavsr.ops`` live in the package namespace alone: no submodule binds an upper-case
+    bool / int / float / str / None / tuple that the package binds too (a copy would make a route-comparison test, which flips
+    ``ops.<NAME>`` in-process, compare a route with itself and pass), and what a test assigns on the package is what a submodule
+    reads through its ``ops`` reference.  The race amplifier's state is ``streams``' own and is not re-exported."""
+    ops, subs = _ops_submodules()
+    assert len(subs) >= 12 and all(hasattr(s, "__all__") for s in subs)
+    kinds = (bool, int, float, str, type(None), tuple)
+    switches = [n for n, v in vars(ops).items() if n.isupper() and not n.startswith("_") and isinstance(v, kinds)]
+    assert len(switches) >= 36 and {"PROFILE", "LAYER_C", "MERGE_ROWS", "LN_BWD_DROP", "CONV_TAPSKIP", "FFN2", "WGRAD_BESIDE"} <= set(switches)
+    copies = [(s.__name__, n) for s in subs for n, v in vars(s).items() if n.isupper() and isinstance(v, kinds) and n in vars(ops)]
+    assert not copies, copies
+    assert not hasattr(ops, "RACE_PROBE_US") and not hasattr(ops, "RACE_PROBE_MODE") and not hasattr(ops, "_PROBE_TICK")
+    readers = [s for s in subs if hasattr(s, "ops")]
+    assert len(readers) >= 6 and all(s.ops is ops for s in readers)
+    keep = {n: getattr(ops, n) for n in switches}
+    try:
+        for n in switches:
+            sentinel = object()
+            setattr(ops, n, sentinel)
+            assert all(getattr(s.ops, n) is sentinel for s in readers), n
+    finally:
+        for n, v in keep.items():
+            setattr(ops, n, v)
+    assert all(getattr(ops, n) is v for n, v in keep.items())
+
+
+def test_ops_package_keeps_every_public_name_of_the_one_file_module():
+    """tests/golden/ops_public_names.txt: the public names of ``tavsr/ops.py`` as it stood before it became a package (less
+    RACE_PROBE_US / RACE_PROBE_MODE, now private to ``streams``); the package exposes all of them, and the underscore names the
+    tree reaches from outside."""
+    from tavsr import ops
+    want = open(os.path.join(ROOT, "tests", "golden", "ops_public_names.txt")).read().split()
+    assert len(want) > 200 and "gemm" in want and "rnnt_tsd_step" in want
+    missing = [n for n in want if not hasattr(ops, n)]
+    assert not missing, missing
+    for n in ("_addr", "_new_token", "_attn_desc", "_tapskip", "_tapskip2", "_tapskip_any"):
+        assert callable(getattr(ops, n)), n
