@@ -1000,8 +1000,9 @@ int tavsr_embed_bwd(const int64_t* ids, const float* dout, float scale, float* d
  *   im2col2d / col2im2d : KHxKW patches, stride, zero padding (conv3x3 of BasicBlock resnet.py:8-22, 1x1 shortcut
  *                         conv :25-41); col rows (n,ho,wo), columns (kh*KW+kw)*C + c; col2im is the gather-form adjoint
  *   im2col_stem         : Conv3d(1->64, k (5,7,7), s (1,2,2), p (2,3,3)) patches of x[B,T,H,W], 245 taps padded to 256
- *   bn_stats            : training-mode BatchNorm statistics over the M rows (two-pass, deterministic): mean, biased
- *                         var, rstd; running_mean/var/num_batches_tracked updated like torch.nn.BatchNorm (may be NULL)
+ *   bn_stats            : training-mode BatchNorm statistics over the M rows (one read of x, shifted sums kept in double,
+ *                         deterministic): mean, biased var, rstd; running_mean/var/num_batches_tracked updated like
+ *                         torch.nn.BatchNorm (may be NULL); ws >= tavsr_bn_ws floats, 8-byte aligned (it holds doubles)
  *   bn_apply_fwd        : y = act((x - mean) * rstd * gamma + beta (+ res)), act in {none, swish}
  *   bn_bwd              : dz = dy * act'(z) (z recomputed; dz is also d/d res), dgamma, dbeta, dx; ws >= tavsr_bn_ws floats
  *   rsqrt_eps           : out = 1 / sqrt(v + eps)  (eval-mode BatchNorm: rstd from running_var)

@@ -100,38 +100,57 @@ __global__ __launch_bounds__(256) void im2col_stem_kernel(const float* __restric
 }
 
 // ---- BatchNorm (training mode: batch statistics over the M rows of [M, C]) ----------------------------------
-// Single pass: per-block partial sums of (x - s) and (x - s)^2 with the shift s[c] = x[0][c] (any sample is within a few
-// sigma of the mean, so var = E[(x-s)^2] - E[x-s]^2 loses no digits to cancellation): part[blk][2][C].  One read of x
-// instead of the two of the mean-then-variance form.
+// Single pass: per-block partial sums of (x - s) and (x - s)^2 with the shift s[c] = x[0][c]: part[blk][2][C], in DOUBLE.  One read
+// of x instead of the two of the mean-then-variance form.  var = E[(x-s)^2] - E[x-s]^2 cancels K^2 of the sums' leading digits,
+// K = |s - mean| / sigma, so sums kept in fp32 are only good while the one sample x[0] is typical: with row 0 at 10 / 100 / 1000
+// sigma (the zero-padded corner pixel of the first frame is the least typical row there is) they lost 1e-5 ... 1e-3 of the variance
+// (tests/test_gpu_bn_pool_edges.py, profiles/bn_pool_edges.txt).  A mean of R leading rows as the shift only divides K by R.  Double
+// differences and sums lose 1e-16 K^2 whatever the shift is, for 4 double-rate operations per 4 bytes read: with one row per lane
+// in flight that cost 0.2 ms of the 77 ms benchmark step, with four rows in flight (same summation order) nothing against fp32 sums.
 __global__ __launch_bounds__(256) void bn_partial2_kernel(const float* __restrict__ x, int64_t M, int C,
-                                                          int64_t rows_per_block, float* __restrict__ part) {
-  __shared__ float4 red[16][2][16];
+                                                          int64_t rows_per_block, double* __restrict__ part) {
+  __shared__ double red[16][2][16][4];
   const int cq = threadIdx.x & 15, ry = threadIdx.x >> 4;
   const int c = blockIdx.x * 64 + cq * 4;
   const int64_t r0 = (int64_t)blockIdx.y * rows_per_block, r1 = min(M, r0 + rows_per_block);
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  double s1[4] = {0.0, 0.0, 0.0, 0.0}, s2[4] = {0.0, 0.0, 0.0, 0.0};
   if (c < C) {
-    const float4 sh = *reinterpret_cast<const float4*>(x + c);
-    for (int64_t r = r0 + ry; r < r1; r += 16) {
-      const float4 v = *reinterpret_cast<const float4*>(x + r * C + c);
-      const float a = v.x - sh.x, b = v.y - sh.y, cc = v.z - sh.z, d = v.w - sh.w;
-      s1.x += a; s1.y += b; s1.z += cc; s1.w += d;
-      s2.x += a * a; s2.y += b * b; s2.z += cc * cc; s2.w += d * d;
+    const float4 sh4 = *reinterpret_cast<const float4*>(x + c);
+    const double sh[4] = {(double)sh4.x, (double)sh4.y, (double)sh4.z, (double)sh4.w};
+    for (int64_t r = r0 + ry; r < r1; r += 64) {      // four rows of this lane in flight (one load per trip waits out its latency alone)
+      float4 v4[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u)      // past the block's end: row 0, the shift itself, which adds 0 to both sums
+        v4[u] = *reinterpret_cast<const float4*>(x + (r + 16 * u < r1 ? (r + 16 * u) * C : 0) + c);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const float v[4] = {v4[u].x, v4[u].y, v4[u].z, v4[u].w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const double a = (double)v[j] - sh[j];      // exact
+          s1[j] += a;
+          s2[j] += a * a;
+        }
+      }
     }
   }
-  red[ry][0][cq] = s1;
-  red[ry][1][cq] = s2;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { red[ry][0][cq][j] = s1[j]; red[ry][1][cq][j] = s2[j]; }
   __syncthreads();
   if (ry < 2 && c < C) {
-    float4 t = red[0][ry][cq];
+    double* out = part + ((int64_t)blockIdx.y * 2 + ry) * C + c;
 #pragma unroll
-    for (int k = 1; k < 16; ++k) { const float4 u = red[k][ry][cq]; t.x += u.x; t.y += u.y; t.z += u.z; t.w += u.w; }
-    *reinterpret_cast<float4*>(part + ((int64_t)blockIdx.y * 2 + ry) * C + c) = t;
+    for (int j = 0; j < 4; ++j) {
+      double t = red[0][ry][cq][j];
+#pragma unroll
+      for (int k = 1; k < 16; ++k) t += red[k][ry][cq][j];
+      out[j] = t;
+    }
   }
 }
 
 // mean, biased variance, rstd and the running statistics from the single-pass partials (combined in double)
-__global__ __launch_bounds__(1024) void bn_finalize2_kernel(const float* __restrict__ part, int nparts, int C, int64_t M,
+__global__ __launch_bounds__(1024) void bn_finalize2_kernel(const double* __restrict__ part, int nparts, int C, int64_t M,
                                                             const float* __restrict__ x, float eps, float momentum,
                                                             float* __restrict__ mean, float* __restrict__ var,
                                                             float* __restrict__ rstd, float* __restrict__ running_mean,
@@ -143,16 +162,16 @@ __global__ __launch_bounds__(1024) void bn_finalize2_kernel(const float* __restr
   if (c < C) {
     int p = g;
     for (; p + 48 < nparts; p += 64) {      // four loads of each stream in flight; the sums stay in partial order
-      const float a0 = part[((int64_t)p * 2 + 0) * C + c], a1 = part[((int64_t)(p + 16) * 2 + 0) * C + c];
-      const float a2 = part[((int64_t)(p + 32) * 2 + 0) * C + c], a3 = part[((int64_t)(p + 48) * 2 + 0) * C + c];
-      const float b0 = part[((int64_t)p * 2 + 1) * C + c], b1 = part[((int64_t)(p + 16) * 2 + 1) * C + c];
-      const float b2 = part[((int64_t)(p + 32) * 2 + 1) * C + c], b3 = part[((int64_t)(p + 48) * 2 + 1) * C + c];
-      a += (double)a0; a += (double)a1; a += (double)a2; a += (double)a3;
-      b += (double)b0; b += (double)b1; b += (double)b2; b += (double)b3;
+      const double a0 = part[((int64_t)p * 2 + 0) * C + c], a1 = part[((int64_t)(p + 16) * 2 + 0) * C + c];
+      const double a2 = part[((int64_t)(p + 32) * 2 + 0) * C + c], a3 = part[((int64_t)(p + 48) * 2 + 0) * C + c];
+      const double b0 = part[((int64_t)p * 2 + 1) * C + c], b1 = part[((int64_t)(p + 16) * 2 + 1) * C + c];
+      const double b2 = part[((int64_t)(p + 32) * 2 + 1) * C + c], b3 = part[((int64_t)(p + 48) * 2 + 1) * C + c];
+      a += a0; a += a1; a += a2; a += a3;
+      b += b0; b += b1; b += b2; b += b3;
     }
     for (; p < nparts; p += 16) {
-      a += (double)part[((int64_t)p * 2 + 0) * C + c];
-      b += (double)part[((int64_t)p * 2 + 1) * C + c];
+      a += part[((int64_t)p * 2 + 0) * C + c];
+      b += part[((int64_t)p * 2 + 1) * C + c];
     }
   }
   red[g][0][cx] = a;
@@ -582,20 +601,23 @@ extern "C" int tavsr_im2col_stem(const float* x, float* col, int32_t B, int32_t 
   return TAVSR_OK;
 }
 
-extern "C" int64_t tavsr_bn_ws(int64_t M, int32_t C) { return (int64_t)bn_chunks(M) * 2 * C; }
+// floats: tavsr_bn_stats keeps its [chunks][2][C] partial sums as doubles; the backward passes use [chunks][2][C] floats of it
+extern "C" int64_t tavsr_bn_ws(int64_t M, int32_t C) { return (int64_t)bn_chunks(M) * 4 * C; }
 
 extern "C" int tavsr_bn_stats(const float* x, int64_t M, int32_t C, float eps, float momentum, float* mean, float* var,
                               float* rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* ws,
                               tavsr_stream_t stream) {
   TAVSR_REQUIRE(x && mean && var && rstd && ws, TAVSR_EINVAL, "bn_stats: null pointer");
   TAVSR_REQUIRE(M > 0 && C > 0, TAVSR_EINVAL, "bn_stats: empty input");
-  TAVSR_REQUIRE(C % 4 == 0 && ((uintptr_t)x & 15) == 0, TAVSR_EUNSUPPORTED, "bn_stats: C %% 4 == 0 and 16-byte aligned rows required");
+  TAVSR_REQUIRE(C % 4 == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)ws & 7) == 0, TAVSR_EUNSUPPORTED,
+                "bn_stats: C %% 4 == 0, 16-byte aligned rows and an 8-byte aligned workspace required");
   hipStream_t s = (hipStream_t)stream;
   const int chunks = bn_chunks(M);
   const int64_t rpb = (M + chunks - 1) / chunks;
   const dim3 g(cdiv(C, 64), chunks);
-  hipLaunchKernelGGL(bn_partial2_kernel, g, dim3(256), 0, s, x, M, C, rpb, ws);
-  hipLaunchKernelGGL(bn_finalize2_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, ws, chunks, C, M, x, eps, momentum, mean, var, rstd,
+  double* part = reinterpret_cast<double*>(ws);                  // [chunks][2][C] doubles = tavsr_bn_ws(M, C) floats
+  hipLaunchKernelGGL(bn_partial2_kernel, g, dim3(256), 0, s, x, M, C, rpb, part);
+  hipLaunchKernelGGL(bn_finalize2_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const double*)part, chunks, C, M, x, eps, momentum, mean, var, rstd,
                      running_mean, running_var, num_batches_tracked);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
