@@ -158,13 +158,14 @@ typedef struct tavsr_gemm_desc {
   int32_t conv_posmajor;          /* see the conv fields above; it sits in what was padding, so no other field moves */
   const uint64_t* drop_seed;
   uint64_t drop_offset;
-  /* optional [M][ceil(N / 64)][2]: per row and 64-column tile, sum and sum of squares of the stored C values (after bias /
-     activation / alpha / residual) - LayerNorm statistics of the result without another pass over it (cgMLP: the gate half of
-     channel_proj1's output, consumed by tavsr_csgu_fwd).  Unbatched problems on the 16-byte path, no K split; otherwise
-     TAVSR_EUNSUPPORTED and nothing is launched. */
+  /* optional [M][ceil(N / 64)][2]: per row and 64-column tile, (sum, M2) of the stored C values (after bias / activation /
+     alpha / residual), M2 = sum of squared deviations from the tile's own mean over its min(64, N - 64 * tile) columns - never a
+     raw sum of squares, so that merging tiles (Chan's update) does not cancel on rows whose mean dwarfs their spread.  LayerNorm
+     statistics of the result without another pass over it (cgMLP: the gate half of channel_proj1's output, consumed by
+     tavsr_csgu_fwd).  Unbatched problems on the 16-byte path, no K split; otherwise TAVSR_EUNSUPPORTED and nothing is launched. */
   float* rowstat;
   /* with rowstat: per row and 64-column tile the two weighted sums (sum_n C[m][n] * rowdot_a[n], sum_n C[m][n] * rowdot_b[n]) instead of
-     (sum, sum of squares) - the learned-average merge's pooling / branch-weight projections of a branch output (encoder_layer.py:
+     (sum, M2) - the learned-average merge's pooling / branch-weight projections of a branch output (encoder_layer.py:
      246-280: pooling_proj_k, weight_proj_k are Linear(d, 1)) taken where the branch's last Linear stores its rows, so that
      tavsr_merge_proj_fwd does not re-read both branch outputs of the whole utterance per workgroup.  [N] each, 16-byte aligned; both or
      neither. */
@@ -483,7 +484,8 @@ int tavsr_csgu_fwd(const float* g, int64_t ldg, const float* ln_w, const float* 
                    const uint64_t* seed_dev, uint64_t offset, int32_t B, int32_t T, int32_t C, int32_t K,
                    const float* rowstat, tavsr_stream_t stream);
 /* rowstat (optional): the tavsr_gemm_desc.rowstat output of the GEMM that produced g ([B*T][ldg / 64][2]): the statistics launch is
- * skipped, the gate rows' mean / rstd come from the C / 64 gate tiles' partial sums (C <= 1024) and are still written out. */
+ * skipped, the gate rows' mean / rstd come from the C / 64 gate tiles' (sum, M2) pairs (C <= 1024; whole 64-column tiles, merged by the
+ * equal-count Chan update: mean = avg of the tile means, C * var = sum M2_t + 64 * sum (mean_t - mean)^2) and are still written out. */
 int64_t tavsr_dwconv_gate_bwd_ws(int32_t B, int32_t T, int32_t C, int32_t K);
 int tavsr_dwconv_gate_bwd(const float* du, const float* gn, const float* r, int64_t ldr, const float* conv,
                           const float* w, float* dr, int64_t lddr, float* dgn, float* dw, float* dbias,

@@ -28,7 +28,7 @@ def main():
         # with the LayerNorm statistics from channel_proj1's epilogue (the layer's form: no statistics launch)
         gg = g[:, Cn:].double().view(B * T, Cn // 64, 64)
         rst = torch.zeros(B * T, 2 * Cn // 64, 2, device="cuda")
-        rst[:, Cn // 64:, 0], rst[:, Cn // 64:, 1] = gg.sum(-1).float(), (gg * gg).sum(-1).float()
+        rst[:, Cn // 64:, 0], rst[:, Cn // 64:, 1] = gg.sum(-1).float(), ((gg - gg.mean(-1, keepdim=True)) ** 2).sum(-1).float()
         print(f"{mode:6s} tavsr_csgu_fwd, statistics given     {timed(lambda: ops.csgu_fwd(g, lw, lb, 1e-12, w, bias, B, T, p=p, save=save, rowstat=rst)):7.1f} us", flush=True)
 
 

@@ -132,9 +132,9 @@ __global__ __launch_bounds__(256, 2) void csgu_fwd_kernel(const float* __restric
                                                        const uint64_t* __restrict__ seed, uint64_t offset4,
                                                        const float* __restrict__ rowstat, int stat_ld, float eps,
                                                        float* __restrict__ mean_out, float* __restrict__ rstd_out) {
-  // rowstat != null: the statistics come as per-row partial (sum, sum of squares) pairs of the 64-column tiles of the GEMM
-  // that produced g ([rows][stat_ld][2]; the gate half is tiles C / 64 ..): the 16 lanes that load a row fetch one pair each
-  // and reduce; block 0 writes mean / rstd out for the backward pass.
+  // rowstat != null: the statistics come as per-row partial (sum, M2 about the tile's own mean) pairs of the 64-column tiles
+  // of the GEMM that produced g ([rows][stat_ld][2]; the gate half is tiles C / 64 ..): the 16 lanes that load a row fetch one
+  // pair each and merge them; block 0 writes mean / rstd out for the backward pass.
   constexpr int pad = (K - 1) / 2, rows = CG_TT + K - 1;
   __shared__ __attribute__((aligned(16))) float s_x[rows * CG_CH];
   __shared__ float s_w[CG_CH * K];
@@ -181,12 +181,18 @@ __global__ __launch_bounds__(256, 2) void csgu_fwd_kernel(const float* __restric
     if (rowstat) {
 #pragma unroll
       for (int q = 0; q < NP; ++q) {
-        float s1 = sp[q].x, s2 = sp[q].y;
+        // equal-count Chan merge of the nt tiles (every gate tile is a whole 64 columns): mean = avg of the tile means,
+        // C var = sum M2_t + 64 sum (mean_t - mean)^2 - never from raw second moments (no cancellation)
+        float s1 = sp[q].x;
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o, 64); s2 += __shfl_xor(s2, o, 64); }
+        for (int o = 8; o > 0; o >>= 1) s1 += __shfl_xor(s1, o, 64);
         const float m_ = s1 / (float)C;
+        const float dm = l4 < (C >> 6) ? sp[q].x * (1.f / 64.f) - m_ : 0.f;
+        float s2 = sp[q].y + 64.f * dm * dm;
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s2 += __shfl_xor(s2, o, 64);
         mu[q] = m_;
-        rs[q] = rsqrtf(fmaxf(s2 / (float)C - m_ * m_, 0.f) + eps);
+        rs[q] = rsqrtf(s2 / (float)C + eps);
         const int i = rr + 16 * q, t = t0 + i - pad;
         if (mean_out && blockIdx.x == 0 && l4 == 0 && i >= pad && i < pad + CG_TT && t < T) {
           mean_out[(int64_t)b * T + t] = mu[q];

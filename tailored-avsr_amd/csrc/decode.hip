@@ -918,7 +918,7 @@ __global__ __launch_bounds__(WPB * 64) void rowlin_kernel(RowLinArgs a) {
   constexpr int NACC = R * R / 64;          // accumulator registers (4 / 16)
   typedef float accv __attribute__((ext_vector_type(NACC)));
   __shared__ float s_acc[WPB][NACC][64];
-  __shared__ float s_red[2][WPB][R];
+  __shared__ float s_red[3][WPB][R];          // per wave and row: mean - pivot, M2, pivot
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int r = lane & (R - 1), g = lane / R;
   const int col0 = blockIdx.x * R;
@@ -970,6 +970,13 @@ __global__ __launch_bounds__(WPB * 64) void rowlin_kernel(RowLinArgs a) {
     //   mean = avg_w mean_w,   K var = sum_w M2_w + KW sum_w (mean_w - mean)^2
     // - the deviations are taken from a mean, never from raw second moments (no cancellation), and the second barrier + LDS round
     // of a global two-pass form is gone (1.3 us of a 4.9 us launch went into the statistics).
+    // Every sum is taken of x - pivot, the pivot being the row's first element of the wave's slice: on a row whose mean dwarfs its
+    // spread x - pivot is exact, the sums are of the size of the spread, and the mean is carried as pivot + a small float - so the
+    // normalised row is as accurate as on a row without offset (a mean held in ONE float is off by up to an ulp of |mean|, which a
+    // row of mean 100 sigma shows as 1e-5 of the output).
+    const float pv = __shfl(av[0].x, r, 64);          // lane (r, g = 0) holds the row's first element
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) { av[j].x -= pv; av[j].y -= pv; av[j].z -= pv; av[j].w -= pv; }
     float sm = 0.f;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) sm += (av[j].x + av[j].y) + (av[j].z + av[j].w);
@@ -984,16 +991,16 @@ __global__ __launch_bounds__(WPB * 64) void rowlin_kernel(RowLinArgs a) {
     }
 #pragma unroll
     for (int o = R; o < 64; o <<= 1) sq += __shfl_xor(sq, o, 64);
-    if (g == 0) { s_red[0][wave][r] = mw; s_red[1][wave][r] = sq; }
+    if (g == 0) { s_red[0][wave][r] = mw; s_red[1][wave][r] = sq; s_red[2][wave][r] = pv; }
     __syncthreads();
-    float mean = 0.f;
+    float mean = 0.f;                                 // the row's mean minus this wave's pivot
 #pragma unroll
-    for (int w = 0; w < WPB; ++w) mean += s_red[0][w][r];
+    for (int w = 0; w < WPB; ++w) mean += (s_red[2][w][r] - pv) + s_red[0][w][r];
     mean *= 1.f / (float)WPB;
     float var = 0.f, dm2 = 0.f;
 #pragma unroll
     for (int w = 0; w < WPB; ++w) {
-      const float d = s_red[0][w][r] - mean;
+      const float d = (s_red[2][w][r] - pv) + s_red[0][w][r] - mean;
       var += s_red[1][w][r];
       dm2 += d * d;
     }

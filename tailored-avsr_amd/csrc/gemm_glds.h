@@ -318,8 +318,8 @@ __device__ __forceinline__ void finish_tile_vec(const tavsr_gemm_desc& d, int ns
     }
     *reinterpret_cast<float4*>(base + o) = v;
     }
-    if (rowstat) {       // the 16 lanes that share a row of a 64-wide tile: sum and sum of squares of what was stored ...
-      float s1 = ok ? (v.x + v.y) + (v.z + v.w) : 0.f, s2 = ok ? (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w) : 0.f;
+    if (rowstat) {       // the 16 lanes that share a row of a 64-wide tile: sum of what was stored and M2 about the tile's own mean ...
+      float s1 = ok ? (v.x + v.y) + (v.z + v.w) : 0.f, s2 = 0.f;
       if (d.rowdot_a) {  // ... or its two weighted sums (tavsr_gemm_desc.rowdot_a / _b: the merge's pooling and branch-weight projections)
         const float4 wa = ok ? *reinterpret_cast<const float4*>(d.rowdot_a + n) : make_float4(0.f, 0.f, 0.f, 0.f);
         const float4 wb = ok ? *reinterpret_cast<const float4*>(d.rowdot_b + n) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -327,7 +327,14 @@ __device__ __forceinline__ void finish_tile_vec(const tavsr_gemm_desc& d, int ns
         s2 = (v.x * wb.x + v.y * wb.y) + (v.z * wb.z + v.w * wb.w);
       }
 #pragma unroll
-      for (int o2 = 8; o2 > 0; o2 >>= 1) { s1 += __shfl_xor(s1, o2, 64); s2 += __shfl_xor(s2, o2, 64); }
+      for (int o2 = 8; o2 > 0; o2 >>= 1) s1 += __shfl_xor(s1, o2, 64);
+      if (!d.rowdot_a && ok) {   // deviations from the tile mean (of its min(64, N - n0) valid columns), never raw squares: no cancellation
+        const float tm = s1 / (float)min(64, d.N - n0);
+        const float e0 = v.x - tm, e1 = v.y - tm, e2 = v.z - tm, e3 = v.w - tm;
+        s2 = (e0 * e0 + e1 * e1) + (e2 * e2 + e3 * e3);
+      }
+#pragma unroll
+      for (int o2 = 8; o2 > 0; o2 >>= 1) s2 += __shfl_xor(s2, o2, 64);
       if (c4 == 0 && mv < d.M)
         *reinterpret_cast<float2*>(d.rowstat + ((int64_t)m * ((d.N + 63) / 64) + n0 / 64) * 2) = make_float2(s1, s2);
     }

@@ -72,7 +72,7 @@ def gemm(M, N, K, A, lda, B, ldb, Cc, ldc, *, a_off=0, b_off=0, c_off=0, a_kmajo
         d.a_rowsum = _addr(a_rowsum)
     if drop is not None:        # dropout token (p, offset, seed tensor): the mask rides in the epilogue
         d.drop_p, d.drop_offset, d.drop_seed = drop[0], drop[1], _addr(drop[2])
-    if rowstat is not None:     # [M, ceil(N / 64), 2]: per-row (sum, sum of squares) of every 64-column tile of the result
+    if rowstat is not None:     # [M, ceil(N / 64), 2]: per-row (sum, M2 about the tile's own mean) of every 64-column tile of the result
         d.rowstat = _addr(rowstat)
         if rowdot is not None:  # ... or the two weighted sums (<rowdot[0], row>, <rowdot[1], row>) per tile (tavsr_gemm_desc.rowdot_*)
             require_cuda(rowdot[0], rowdot[1])
@@ -132,7 +132,8 @@ def gemm(M, N, K, A, lda, B, ldb, Cc, ldc, *, a_off=0, b_off=0, c_off=0, a_kmajo
 def linear(x, w, b=None, *, act=None, alpha=1.0, res=None, save_z=False, out=None, out_off=0, ldc=None, force=None,
            rowstat=None, ln=None):
     """y = res + alpha*act(x @ w.T + b); x [M,K] (row stride x.stride(0)), w [N,K] torch layout.  ``rowstat`` (tensor
-    [M, ceil(N / 64), 2]): receives the per-row (sum, sum of squares) of every 64-column tile of y (tavsr_gemm_desc.rowstat).
+    [M, ceil(N / 64), 2]): receives the per-row (sum, M2 = sum of squared deviations from the tile's own mean) of every 64-column tile of y
+    (tavsr_gemm_desc.rowstat).
     ``ln`` = (gamma, beta, eps): also returns LayerNorm(y) - (y, normed) - from the launch that finishes the rows (tavsr_gemm_ln)."""
     M, K = x.shape
     N = w.shape[0]
