@@ -520,6 +520,27 @@ int tavsr_dwconv_add_bwd(const float* du, int64_t lddu, const float* x, int64_t 
                          tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Conformer's convolution module between its pointwise convolutions (csrc/conformer_conv.hip; espnet conformer/convolution.py,
+ * ConvolutionModule.forward: depthwise_conv(glu(pointwise_conv1(x), dim=1))): the GLU and the depthwise convolution in one pass,
+ *   g[b,t,c] = h[b,t,c] * sigmoid(h[b,t,C+c]),   z[b,t,c] = bias[c] + sum_j w[c,j] * g[b, t + j - (K-1)/2, c]
+ * (g = 0 outside 0 <= t < T: the halo stops at the utterance).  h: [B*T][ldh] with 2C channels (ldh >= 2C), z: [B*T][ldz]
+ * (ldz >= C), w: [C][K] (torch [C,1,K]), bias: [C].  T is dense: the kernel knows no lengths.  g is never stored.
+ * bwd, from dz [B*T][lddz], with dg[t] = sum_k w[k] dz[t + (K-1)/2 - k] and s = sigmoid(h[.., C+c]):
+ *   dh[.., c] = dg * s,  dh[.., C+c] = dg * h[.., c] * s * (1 - s)      (dh: [B*T][lddh], lddh >= 2C; columns >= 2C untouched)
+ *   dw[c,j] = sum_{b,t} dz[b,t,c] g[b,t+j-(K-1)/2,c],  dbias[c] = sum_{b,t} dz[b,t,c]      (overwritten)
+ * dw and dbias are reduced in a fixed order (per-block partial slabs in ws, then tavsr_sum_partials): no float atomics, the
+ * same bits every run.  ws >= tavsr_glu_dwconv_bwd_ws(B, T, C, K) floats.
+ * tavsr_glu_dwconv_ok: 1 for K odd, 1 <= K <= 31 and 1 <= B <= 65535, T >= 1, C >= 1 with B * T < 2^31; where it is 0 the
+ * entries return TAVSR_EUNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_glu_dwconv_ok(int32_t B, int32_t T, int32_t C, int32_t K);
+int tavsr_glu_dwconv_fwd(const float* h, int64_t ldh, const float* w, const float* bias, float* z, int64_t ldz,
+                         int32_t B, int32_t T, int32_t C, int32_t K, tavsr_stream_t stream);
+int64_t tavsr_glu_dwconv_bwd_ws(int32_t B, int32_t T, int32_t C, int32_t K);
+int tavsr_glu_dwconv_bwd(const float* dz, int64_t lddz, const float* h, int64_t ldh, const float* w, float* dh, int64_t lddh,
+                         float* dw, float* dbias, float* ws, int32_t B, int32_t T, int32_t C, int32_t K, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * The tailored audio-visual encoder layer (csrc/layer.hip): TailoredEncoderLayer.forward
  * (src/encoder/audiovisual/tailored/encoder_layer.py:118-274).  Each modality stream runs  macaron FFN -> ONE branch (rel-pos
  * attention or cgMLP, per layer and modality: encoder.py's acoustic_use_attn / visual_use_attn lists) with its residual -> FFN ->

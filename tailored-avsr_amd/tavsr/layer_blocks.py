@@ -1,5 +1,6 @@
 """The blocks an encoder layer is sequenced from, each written once: the feed-forward block, the attention cores, the
-relative-position attention branch and the cgMLP branch, with the state each keeps for its backward as a named tuple.
+relative-position attention branch, the cgMLP branch and the Conformer convolution module, with the state each keeps for its
+backward as a named tuple.
 
 ``tavsr.functional`` (Branchformer layer, decoder) and ``tavsr.functional_av`` (tailored audio-visual stream) order these
 blocks; the C sequencers of csrc/layer.hip leave the same state behind (``functional._layer_sv``, ``functional_av._ts_c_desc``)
@@ -383,3 +384,81 @@ class CgmlpBranch:
             ops.act_bwd_(dg, s.z, "gelu")
         G["cgmlp.channel_proj1.0.weight"], G["cgmlp.channel_proj1.0.bias"] = grp.add(dg, s.n, bias_grad=True)
         return ops.linear_dx(dg, p["cgmlp.channel_proj1.0.weight"])
+
+
+# the eight parameters of the Conformer convolution module behind its LayerNorm, in the order ConvModuleBlock reads them
+CONV_PARAMS = ("conv_module.pointwise_conv1.weight", "conv_module.pointwise_conv1.bias", "conv_module.depthwise_conv.weight",
+               "conv_module.depthwise_conv.bias", "conv_module.norm.weight", "conv_module.norm.bias",
+               "conv_module.pointwise_conv2.weight", "conv_module.pointwise_conv2.bias")
+BN_EPS, BN_MOMENTUM = 1e-5, 0.1      # torch.nn.BatchNorm1d defaults (espnet's ConvolutionModule sets neither)
+
+
+class ConvSaved(NamedTuple):
+    """kept by the convolution module: its input rows, the statistics of ``norm_conv`` and its output ``n``, pointwise_conv1's
+    output ``h`` [M, 2C] (the GLU's input: the gated rows are never stored), the depthwise convolution's output ``z``, the
+    BatchNorm statistics used (batch statistics in training), the activated rows ``y`` that pointwise_conv2 reads and the token
+    of the layer's dropout on the module's output."""
+    x: Any
+    mean: Any
+    rstd: Any
+    n: Any
+    h: Any
+    z: Any
+    bmean: Any
+    brstd: Any
+    y: Any
+    t_out: Any
+
+
+class ConvModuleBlock:
+    """y = x + drop(pointwise_conv2(act(BatchNorm(depthwise_conv(glu(pointwise_conv1(LN(x))))))))   (espnet conformer/
+    encoder_layer.py: x = residual + dropout(conv_module(norm_conv(x))); conformer/convolution.py).  The 1x1 convolutions are
+    GEMMs on [M, .] rows, GLU + depthwise convolution one kernel (ops.glu_dwconv_fwd), BatchNorm the channels-last kernels of the
+    lip front-end over all M = B*T rows, padded ones included - espnet masks nothing here.  ``bn`` = (running_mean, running_var,
+    num_batches_tracked); a training forward updates them on the device, also without a backward to follow.
+    ``ln_w is None``: the module alone (espnet ConvolutionModule.forward) - no LayerNorm in front, no residual, no dropout."""
+
+    @staticmethod
+    def fwd(x, ln_w, ln_b, p, bn, B, T, act, training, pd=0.0):
+        w1, wd, w2 = (p[CONV_PARAMS[0]], p[CONV_PARAMS[2]], p[CONV_PARAMS[6]])
+        Cn = wd.shape[0]
+        if ln_w is None:
+            n, mean, rstd = x, None, None
+        else:
+            n, mean, rstd = ops.layernorm_fwd(x, ln_w, ln_b, EPS_ESPNET)
+        h = ops.linear(n, w1.reshape(2 * Cn, Cn), p[CONV_PARAMS[1]])
+        z = ops.glu_dwconv_fwd(h, wd.reshape(Cn, -1), p[CONV_PARAMS[3]], B, T)
+        if training:
+            bmean, brstd = ops.bn_stats(z, BN_EPS, BN_MOMENTUM, *bn)
+        else:
+            bmean, brstd = bn[0], ops.rsqrt_eps(bn[1], BN_EPS)
+        y = ops.bn_apply_fwd(z, bmean, brstd, p[CONV_PARAMS[4]], p[CONV_PARAMS[5]], None, act)
+        if ln_w is None:
+            out, t_out = ops.linear(y, w2.reshape(Cn, Cn), p[CONV_PARAMS[7]]), None
+        else:
+            out, t_out = ops.linear_drop(y, w2.reshape(Cn, Cn), p[CONV_PARAMS[7]], pd, res=x)
+        return out, ConvSaved(x=x, mean=mean, rstd=rstd, n=n, h=h, z=z, bmean=bmean, brstd=brstd, y=y, t_out=t_out)
+
+    @staticmethod
+    def bwd(dy, saved, ln_w, p, B, T, act, grp, lng, G, dyd=None, out_drop=None):
+        """``dy``: gradient of the block's output; ``dyd``: the same under the block's dropout mask where the caller has it.
+        Returns (dx, gln_w, gln_b[, dx under ``out_drop``]) - dx includes the residual path; fills ``G`` with the module's
+        eight gradients (the two 1x1 convolutions' weight gradients through ``grp``)."""
+        s = saved
+        w1, wd, w2 = (p[CONV_PARAMS[0]], p[CONV_PARAMS[2]], p[CONV_PARAMS[6]])
+        Cn = wd.shape[0]
+        if dyd is None:
+            dyd = _drop_bwd(dy, s.t_out)
+        gw2, G[CONV_PARAMS[7]] = grp.add(dyd, s.y, bias_grad=True)
+        G[CONV_PARAMS[6]] = gw2.view_as(w2)
+        da = ops.linear_dx(dyd, w2.reshape(Cn, Cn))
+        _, dz, G[CONV_PARAMS[4]], G[CONV_PARAMS[5]] = ops.bn_bwd(da, s.z, s.bmean, s.brstd, p[CONV_PARAMS[4]], p[CONV_PARAMS[5]], None,
+                                                                 act, need_dz=False)
+        dh, gwd, G[CONV_PARAMS[3]] = ops.glu_dwconv_bwd(dz, s.h, wd.reshape(Cn, -1), B, T)
+        G[CONV_PARAMS[2]] = gwd.view_as(wd)
+        gw1, G[CONV_PARAMS[1]] = grp.add(dh, s.n, bias_grad=True)
+        G[CONV_PARAMS[0]] = gw1.view_as(w1)
+        dn = ops.linear_dx(dh, w1.reshape(2 * Cn, Cn))
+        if ln_w is None:
+            return dn, None, None
+        return lng.bwd(dn, s.x, s.mean, s.rstd, ln_w, dx_add=dy, drop=out_drop)

@@ -17,8 +17,8 @@ from .streams import branch_events, branch_stream, forks_enabled, wgrad_may_go_b
 __all__ = ["ffn2_usable", "ffn2_shape_ok", "ffn2_fwd", "DnSlabs", "ffn2_bwd_dx", "axpby", "scale_dev", "axpby2d", "act_bwd_",
            "dwconv_gate_fwd", "csgu_usable", "csgu_rowstat_ok", "csgu_fwd", "cgmlp_block_ok", "cgmlp_fwd", "cgmlp_bwd",
            "conv2d_subsample_ok", "conv2d_subsample_fwd", "conv2d_subsample_bwd", "dwconv_gate_bwd", "dwconv_add_ok", "dwconv_add_fwd",
-           "dwconv_add_bwd", "merge_pool_fwd", "merge_rows_ok", "merge_fwd", "merge_proj_ok", "merge_proj_fwd", "merge_combine",
-           "merge_bwd", "act_"]
+           "dwconv_add_bwd", "glu_dwconv_ok", "glu_dwconv_fwd", "glu_dwconv_bwd", "merge_pool_fwd", "merge_rows_ok", "merge_fwd",
+           "merge_proj_ok", "merge_proj_fwd", "merge_combine", "merge_bwd", "act_"]
 
 
 def ffn2_usable(x, w1, act) -> bool:
@@ -346,6 +346,43 @@ def dwconv_add_bwd(du, x, w, B, T, dx=None):
     check(lib().tavsr_dwconv_add_bwd(ptr(du), du.stride(0), ptr(x), x.stride(0), ptr(w), ptr(dx), dx.stride(0), ptr(dw), ptr(db), 0,
                                      ptr(ws), B, T, Cn, K, stream()), "tavsr_dwconv_add_bwd")
     return dx, dw, db
+
+
+def glu_dwconv_ok(B, T, Cn, K) -> bool:
+    return bool(lib().tavsr_glu_dwconv_ok(B, T, Cn, K))
+
+
+def glu_dwconv_fwd(h, w, bias, B, T, out=None):
+    """z = depthwise_conv1d_K(glu(h)) over time (the Conformer convolution module between its pointwise convolutions):
+    h [B*T, 2C] rows (any row stride), w [C, K], bias [C] -> z [B*T, C].  The gated rows are never stored.  T is dense: no
+    lengths.  Shapes the kernel does not take are an error (there is no other route)."""
+    M, C2 = h.shape
+    Cn = w.shape[0]
+    require_cuda(h, w, bias)
+    assert M == B * T and C2 == 2 * Cn and h.stride(1) == 1 and w.is_contiguous()
+    if out is None:
+        out = empty(M, Cn, like=h)
+    assert out.shape == (M, Cn) and out.stride(1) == 1
+    check(lib().tavsr_glu_dwconv_fwd(ptr(h), h.stride(0), ptr(w), ptr(bias), ptr(out), out.stride(0), B, T, Cn, w.shape[-1], stream()),
+          "tavsr_glu_dwconv_fwd")
+    return out
+
+
+def glu_dwconv_bwd(dz, h, w, B, T, dh=None):
+    """backward of glu_dwconv_fwd -> (dh [B*T, 2C], dw [C, K], dbias [C]); the gated rows are recomputed from h, dw / dbias are
+    reduced in a fixed order (no atomics)."""
+    M, C2 = h.shape
+    Cn, K = w.shape
+    require_cuda(dz, h, w)
+    assert M == B * T and C2 == 2 * Cn and dz.shape == (M, Cn) and dz.stride(1) == 1 and h.stride(1) == 1 and w.is_contiguous()
+    if dh is None:
+        dh = empty(M, C2, like=h)
+    assert dh.shape == (M, C2) and dh.stride(1) == 1
+    dw, db = empty(Cn, K, like=h), empty(Cn, like=h)
+    ws = empty(max(1, lib().tavsr_glu_dwconv_bwd_ws(B, T, Cn, K)), like=h)
+    check(lib().tavsr_glu_dwconv_bwd(ptr(dz), dz.stride(0), ptr(h), h.stride(0), ptr(w), ptr(dh), dh.stride(0), ptr(dw), ptr(db), ptr(ws),
+                                     B, T, Cn, K, stream()), "tavsr_glu_dwconv_bwd")
+    return dh, dw, db
 
 
 def merge_pool_fwd(x1, x2, lens, params, B, T, lens2=None):

@@ -10,6 +10,7 @@ from ..decoder.mlm_decoder import MLMDecoder
 from ..decoder.transducer_decoder import TransducerDecoder
 from ..decoder.transformer_decoder import TransformerDecoder
 from ..encoder.branchformer.encoder import MyBranchformerEncoder
+from ..encoder.conformer.encoder import ConformerEncoder
 from ..encoder.e_branchformer.encoder import EBranchformerEncoder
 from ..frontend.conv3d_resnet18 import Conv3dResNet18
 from ..frontend.default import DefaultFrontend
@@ -20,7 +21,8 @@ from ..utils.tokens import load_token_list
 
 frontend_choices = {"default": DefaultFrontend, "conv3dresnet18": Conv3dResNet18}      # src/tasks/asr.py:93-103
 specaug_choices = {"specaug": SpecAug}
-encoder_choices = {"branchformer": MyBranchformerEncoder, "e_branchformer": EBranchformerEncoder}      # src/tasks/asr.py:161-162
+encoder_choices = {"conformer": ConformerEncoder, "branchformer": MyBranchformerEncoder,      # src/tasks/asr.py:148,161-162
+                   "e_branchformer": EBranchformerEncoder}
 decoder_choices = {"transformer": TransformerDecoder, "mlm": MLMDecoder, "transducer": TransducerDecoder}
 normalize_choices = {"utterance_mvn": UtteranceMVN}
 model_choices = {"espnet": ESPnetASRModel, "maskctc": MaskCTCModel}
