@@ -468,7 +468,13 @@ int tavsr_scale_dev(const float* x, const float* s, float c, float* out, int64_t
  * encoder_layer.py:220): out = r * (bias + depthwise_conv1d_K(gn)) along time, "same" padding,
  * per utterance; gn = LayerNorm(gate half) is a tavsr_layernorm_fwd call on the strided half.
  *   gn, out, conv: [B*T, C];  r: gate-free half, row stride ldr;  w: [C, K] (torch [C,1,K]).
- * bwd: dr (row stride lddr), dgn, dw, dbias; ws >= tavsr_dwconv_gate_bwd_ws floats.
+ * bwd: dr (row stride lddr), dgn, dw, dbias (overwritten, or added to with accumulate = 1);
+ * ws >= tavsr_dwconv_gate_bwd_ws floats.
+ * K: every odd kernel size from 1 to 63, any C and T (K may be wider than the utterance); an even K, K < 1
+ * or K > 63: TAVSR_EUNSUPPORTED, nothing is launched.  K = 31 runs kernels of its own; every other K the
+ * generic pair, whose dynamic LDS grows with K - forward (127 + 2K) * 256 bytes, backward (126 + 3K) * 256
+ * bytes: 64,768 and 80,640 at K = 63 - and is opted in for (hipFuncAttributeMaxDynamicSharedMemorySize);
+ * where the runtime does not grant that, the call returns TAVSR_EUNSUPPORTED and launches nothing.
  * ------------------------------------------------------------------------------------------- */
 int tavsr_dwconv_gate_fwd(const float* gn, const float* r, int64_t ldr, const float* w, const float* bias,
                           float* out, float* conv, int32_t B, int32_t T, int32_t C, int32_t K,

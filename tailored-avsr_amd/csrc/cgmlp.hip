@@ -985,13 +985,32 @@ __global__ __launch_bounds__(256) void merge_reduce_scatter_kernel(const float* 
 
 using namespace tavsr;
 
+// Dynamic LDS of the two generic gate kernels: the time tile with its halo (and, backward, the dconv tile beside it) plus the
+// K x 64 tap block.  Forward (127 + 2K) * 256 bytes: past 48 KB from K = 33, 64,768 at K = 63; backward (126 + 3K) * 256 bytes:
+// past 48 KB from K = 23, past 64 KB from K = 45, 80,640 at K = 63.  The kernels opt in to their K = CG_KMAX request (as ctc.hip,
+// rnnt.hip, timesync.hip, decode.hip and mergeproj.hip do for theirs), so that every accepted K launches whatever default the
+// runtime enforces - the MI355X's grants 160 KB without being asked (profiles/cgmlp_gate_edges.txt); a runtime that does not
+// grant the request refuses the call, nothing is launched.
+static size_t gate_fwd_lds(int K) { return ((size_t)(CG_TT + K - 1) * CG_CH + (size_t)K * CG_CH) * sizeof(float); }
+static size_t gate_bwd_lds(int K) { return (2 * (size_t)(CG_TB + K - 1) * CG_CH + (size_t)K * CG_CH) * sizeof(float); }
+static int gate_lds_opt_in(const void* fn, size_t bytes, const char* what) {
+  const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  TAVSR_REQUIRE(e == hipSuccess, TAVSR_EUNSUPPORTED, "%s: %zu bytes of dynamic LDS not granted: hipFuncSetAttribute: %s", what, bytes,
+                hipGetErrorString(e));
+  return TAVSR_OK;
+}
+
 extern "C" int tavsr_dwconv_gate_fwd(const float* gn, const float* r, int64_t ldr, const float* w, const float* bias,
                                      float* out, float* conv, int32_t B, int32_t T, int32_t C, int32_t K,
                                      tavsr_stream_t stream) {
   TAVSR_REQUIRE(gn && r && w && bias && out, TAVSR_EINVAL, "dwconv_gate_fwd: null pointer");
   TAVSR_REQUIRE(K >= 1 && K <= CG_KMAX && (K & 1), TAVSR_EUNSUPPORTED, "dwconv_gate_fwd: odd K <= %d required", CG_KMAX);
   if (B <= 0 || T <= 0 || C <= 0) return TAVSR_OK;
-  size_t lds = ((CG_TT + K - 1) * CG_CH + K * CG_CH) * sizeof(float);
+  size_t lds = gate_fwd_lds(K);
+  if (K != 31) {
+    int rc = gate_lds_opt_in(reinterpret_cast<const void*>(dwconv_gate_fwd_kernel), gate_fwd_lds(CG_KMAX), "dwconv_gate_fwd");
+    if (rc) return rc;
+  }
   if (K == 31)
     hipLaunchKernelGGL(dwconv_gate_fwd_kfix_kernel<31>, dim3(cdiv(C, CG_CH), cdiv(T, CG_TT), B), dim3(256),
                        (CG_TT + 30) * CG_CH * sizeof(float), (hipStream_t)stream, gn, r, ldr, w, bias, out, conv, B, T, C);
@@ -1046,7 +1065,11 @@ static int dwconv_gate_bwd_impl(const float* du, const float* gn, const float* r
   TAVSR_REQUIRE(K >= 1 && K <= CG_KMAX && (K & 1), TAVSR_EUNSUPPORTED, "dwconv_gate_bwd: odd K <= %d required", CG_KMAX);
   if (B <= 0 || T <= 0 || C <= 0) return TAVSR_OK;
   hipStream_t s = (hipStream_t)stream;
-  size_t lds = (2 * (CG_TB + K - 1) * CG_CH + K * CG_CH) * sizeof(float);
+  size_t lds = gate_bwd_lds(K);
+  if (K != 31) {
+    int rc = gate_lds_opt_in(reinterpret_cast<const void*>(dwconv_gate_bwd_kernel), gate_bwd_lds(CG_KMAX), "dwconv_gate_bwd");
+    if (rc) return rc;
+  }
   if (K == 31)
     hipLaunchKernelGGL(dwconv_gate_bwd_kfix_kernel<31>, dim3(cdiv(C, CG_CH), B), dim3(256),
                        2 * (CG_TB + 30) * CG_CH * sizeof(float), s, du, gn, r, ldr, conv, w, dr, lddr, dgn, ws, B, T, C, zr, ldz, (int)act);
