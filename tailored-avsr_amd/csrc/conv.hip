@@ -169,11 +169,13 @@ __global__ void transpose_inner_kernel(const float* __restrict__ in, float* __re
   }
 }
 
-// y[b,t,:] = (t < len[b]) ? x[b,t,:] - mean_b : 0 ; mean over valid frames (norm_means only)
+// y[b,t,:] = (t < len[b]) ? x[b,t,:] - mean_b : 0 ; mean over valid frames (norm_means only).  The column sums are double: a
+// thread adds len / 4 rows in sequence, and on an utterance whose mean dwarfs its spread (log-mel of a steady sound) the fp32
+// sum's rounding, ~len / 4 half-ulps of the running sum, is no longer small against x - mean.
 __global__ __launch_bounds__(256) void utt_mvn_kernel(const float* __restrict__ x, const int64_t* __restrict__ lens,
                                                       float* __restrict__ y, int T, int F) {
   __shared__ float s_mean[256];
-  __shared__ float s_part[4][64];
+  __shared__ double s_part[4][64];
   const int b = blockIdx.x;
   const int len = (int)min((int64_t)T, lens[b]);
   const float* xb = x + (int64_t)b * T * F;
@@ -181,12 +183,12 @@ __global__ __launch_bounds__(256) void utt_mvn_kernel(const float* __restrict__ 
   const int fx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   for (int f0 = 0; f0 < F; f0 += 64) {
     int f = f0 + fx;
-    float s = 0.f;
+    double s = 0.0;
     if (f < F)
-      for (int t = ty; t < len; t += 4) s += xb[(int64_t)t * F + f];
+      for (int t = ty; t < len; t += 4) s += (double)xb[(int64_t)t * F + f];
     s_part[ty][fx] = s;
     __syncthreads();
-    if (ty == 0 && f < F) s_mean[f] = ((s_part[0][fx] + s_part[1][fx]) + (s_part[2][fx] + s_part[3][fx])) / (float)len;
+    if (ty == 0 && f < F) s_mean[f] = (float)(((s_part[0][fx] + s_part[1][fx]) + (s_part[2][fx] + s_part[3][fx])) / (double)len);
     __syncthreads();
   }
   for (int64_t i = threadIdx.x; i < (int64_t)T * F; i += 256) {
@@ -202,21 +204,21 @@ __global__ __launch_bounds__(256) void utt_mvn_kernel(const float* __restrict__ 
 constexpr int UM_SLICES = 4;
 __global__ __launch_bounds__(256) void utt_mvn_vec_kernel(const float* __restrict__ x, const int64_t* __restrict__ lens,
                                                           float* __restrict__ y, int T, int F) {
-  __shared__ float4 s_part[256];
+  __shared__ double4 s_part[256];
   __shared__ float4 s_mean[64];
   const int b = blockIdx.y, F4 = F >> 2;
   const int len = (int)min((int64_t)T, lens[b]);
   const float4* xb = reinterpret_cast<const float4*>(x + (int64_t)b * T * F);
   float4* yb = reinterpret_cast<float4*>(y + (int64_t)b * T * F);
   const int groups = 256 / F4, c4 = threadIdx.x % F4, rg = threadIdx.x / F4;
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  double4 acc = make_double4(0.0, 0.0, 0.0, 0.0);
   if (rg < groups) {
     int t = rg;
     for (; t + 3 * groups < len; t += 4 * groups) {
       const float4 a = xb[(int64_t)t * F4 + c4], c = xb[(int64_t)(t + groups) * F4 + c4];
       const float4 d = xb[(int64_t)(t + 2 * groups) * F4 + c4], e = xb[(int64_t)(t + 3 * groups) * F4 + c4];
-      acc.x += (a.x + c.x) + (d.x + e.x); acc.y += (a.y + c.y) + (d.y + e.y);
-      acc.z += (a.z + c.z) + (d.z + e.z); acc.w += (a.w + c.w) + (d.w + e.w);
+      acc.x += ((double)a.x + c.x) + ((double)d.x + e.x); acc.y += ((double)a.y + c.y) + ((double)d.y + e.y);
+      acc.z += ((double)a.z + c.z) + ((double)d.z + e.z); acc.w += ((double)a.w + c.w) + ((double)d.w + e.w);
     }
     for (; t < len; t += groups) {
       const float4 a = xb[(int64_t)t * F4 + c4];
@@ -226,13 +228,13 @@ __global__ __launch_bounds__(256) void utt_mvn_vec_kernel(const float* __restric
   }
   __syncthreads();
   if (threadIdx.x < F4) {
-    float4 m = make_float4(0.f, 0.f, 0.f, 0.f);
+    double4 m = make_double4(0.0, 0.0, 0.0, 0.0);
     for (int g = 0; g < groups; ++g) {
-      const float4 a = s_part[g * F4 + threadIdx.x];
+      const double4 a = s_part[g * F4 + threadIdx.x];
       m.x += a.x; m.y += a.y; m.z += a.z; m.w += a.w;
     }
-    const float inv = 1.f / (float)len;
-    s_mean[threadIdx.x] = make_float4(m.x * inv, m.y * inv, m.z * inv, m.w * inv);
+    const double n = (double)len;
+    s_mean[threadIdx.x] = make_float4((float)(m.x / n), (float)(m.y / n), (float)(m.z / n), (float)(m.w / n));
   }
   __syncthreads();
   const int rows = (T + UM_SLICES - 1) / UM_SLICES, t0 = blockIdx.x * rows, t1 = min(T, t0 + rows);

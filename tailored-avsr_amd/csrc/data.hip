@@ -155,14 +155,21 @@ static double host_i0(double x) {
   return s;
 }
 
-extern "C" int64_t tavsr_resample_len(int64_t n_in, double factor) { return factor > 0.0 ? (int64_t)llround((double)n_in / factor) : 0; }
+// round half to even, as the reference's ``int(round(n_in / factor))`` (llround goes away from zero: 5 samples at factor 2 gave 3)
+extern "C" int64_t tavsr_resample_len(int64_t n_in, double factor) {
+  if (!(factor > 0.0) || n_in <= 0) return 0;
+  const double q = (double)n_in / factor, fl = floor(q), d = q - fl;
+  int64_t r = (int64_t)fl;
+  if (d > 0.5 || (d == 0.5 && (r & 1))) ++r;
+  return r;
+}
 
 extern "C" int tavsr_resample_sinc(const float* x, int64_t n_in, float* y, int64_t n_out, double factor, double rolloff, int32_t zeros,
                                    double beta, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(x && y, TAVSR_EINVAL, "resample_sinc: null pointer");
   TAVSR_REQUIRE(factor > 0.0 && rolloff > 0.0 && rolloff <= 1.0 && zeros > 0 && zeros <= 256 && beta >= 0.0, TAVSR_EINVAL,
                 "resample_sinc: factor > 0, rolloff in (0, 1], 1..256 zero crossings, beta >= 0");
-  if (n_in <= 0 || n_out <= 0) return TAVSR_OK;
+  if (n_in <= 0 || n_out <= 0) return TAVSR_OK;      // an empty result (1 sample at factor 2) has no buffer to name
+  TAVSR_REQUIRE(x && y, TAVSR_EINVAL, "resample_sinc: null pointer");
   const double cutoff = rolloff * (factor > 1.0 ? 1.0 / factor : 1.0);
   hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, n_in, y, n_out, factor,
                      cutoff, (double)zeros / cutoff, beta, 1.0 / host_i0(beta));
