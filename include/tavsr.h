@@ -506,7 +506,7 @@ int tavsr_dwconv_gate_bwd_act(const float* du, const float* gn, const float* r, 
                               tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * E-Branchformer's merge convolution (csrc/dwconv_add.hip; espnet2 e_branchformer_encoder.py, EBranchformerEncoderLayer:
+ * E-Branchformer's merge convolution (csrc/dwconv_time.hip; espnet2 e_branchformer_encoder.py, EBranchformerEncoderLayer:
  * x_concat + depthwise_conv_fusion(x_concat)), a depthwise 1-D convolution over time with its own input added back:
  *   u[b,t,c] = x[b,t,c] + bias[c] + sum_j w[c,j] * x[b, t + j - (K-1)/2, c]      (terms outside 0 <= t < T are zero)
  * x: [B*T][ldx], u: [B*T][ldu] (ldx, ldu >= C), w: [C][K] (torch [C,1,K]), bias: [C].  T is dense: the kernel knows no lengths.
@@ -526,7 +526,7 @@ int tavsr_dwconv_add_bwd(const float* du, int64_t lddu, const float* x, int64_t 
                          tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
- * Conformer's convolution module between its pointwise convolutions (csrc/conformer_conv.hip; espnet conformer/convolution.py,
+ * Conformer's convolution module between its pointwise convolutions (csrc/dwconv_time.hip; espnet conformer/convolution.py,
  * ConvolutionModule.forward: depthwise_conv(glu(pointwise_conv1(x), dim=1))): the GLU and the depthwise convolution in one pass,
  *   g[b,t,c] = h[b,t,c] * sigmoid(h[b,t,C+c]),   z[b,t,c] = bias[c] + sum_j w[c,j] * g[b, t + j - (K-1)/2, c]
  * (g = 0 outside 0 <= t < T: the halo stops at the utterance).  h: [B*T][ldh] with 2C channels (ldh >= 2C), z: [B*T][ldz]

@@ -1,7 +1,7 @@
 """Conformer on the HIP path: forward + backward of 12 encoder layers at B = 32, T = 99, D = 256 (macaron_style, use_cnn_module,
 cnn_module_kernel 31, feed-forward units 2048, dropout 0.1) against the E-Branchformer encoder (use_ffn, macaron_ffn,
 merge_conv_kernel 31, the same feed-forward units, cgMLP units 1024) on the same build in the same run - and the convolution
-module's kernels alone (tavsr_glu_dwconv_fwd / _bwd, csrc/conformer_conv.hip) at B = 32, C = 256, K in {3, 31}, T in {99, 3000}:
+module's kernels alone (tavsr_glu_dwconv_fwd / _bwd, csrc/dwconv_time.hip) at B = 32, C = 256, K in {3, 31}, T in {99, 3000}:
 their time and the bytes they must move (fwd: h in, z out; bwd: dz and h in, dh out) against a float4 copy of as many bytes,
 against tavsr_dwconv_add_* at the same C, K, T, and against torch's own F.glu + F.conv1d(groups=C) chain on the device with its
 transposes, all taken in the same run.

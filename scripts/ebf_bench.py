@@ -1,7 +1,7 @@
 """E-Branchformer on the HIP path: forward + backward of 12 encoder layers at B = 32, T = 99, D = 256 (cgMLP and feed-forward
 units 1024, the recipe's dropout rates), at merge_conv_kernel 3 and 31, against the Branchformer encoder with
 ``merge_method: concat`` at the same sizes on the same build - and the merge convolution's kernels alone
-(tavsr_dwconv_add_fwd / _bwd, csrc/dwconv_add.hip): their time, their share of the step, and the bytes they must move over
+(tavsr_dwconv_add_fwd / _bwd, csrc/dwconv_time.hip): their time, their share of the step, and the bytes they must move over
 that time, at the layer's size (cache resident) and at a size whose working set (not one tensor alone) exceeds the Infinity Cache.
 
 Times are device events around replays of a captured graph (scripts/ffn2_bench.timed).  Writes profiles/ebf_bench.txt."""

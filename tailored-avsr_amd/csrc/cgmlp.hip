@@ -468,24 +468,6 @@ __global__ __launch_bounds__(256) void dwconv_gate_bwd_kfix_kernel(const float* 
   }
 }
 
-// split [C][K+1] summed slab into dw[C][K] and dbias[C]
-__global__ void dwconv_split_kernel(const float* __restrict__ sum, float* __restrict__ dw, float* __restrict__ db, int C,
-                                    int K, int accumulate) {
-  int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= C * (K + 1)) return;
-  int c = i / (K + 1), k = i % (K + 1);
-  float v = sum[i];
-  if (k < K) dw[c * K + k] = accumulate ? dw[c * K + k] + v : v;
-  else db[c] = accumulate ? db[c] + v : v;
-}
-
-int dwconv_split(const float* sum, float* dw, float* dbias, int C, int K, int accumulate, hipStream_t stream) {
-  const int n = C * (K + 1);
-  hipLaunchKernelGGL(dwconv_split_kernel, dim3(cdiv(n, 256)), dim3(256), 0, stream, sum, dw, dbias, C, K, accumulate);
-  TAVSR_LAUNCH_CHECK();
-  return TAVSR_OK;
-}
-
 // ------------------------------- learned_ave merge ---------------------------------------------
 // One 512-thread block per utterance b: waves 0-3 work on branch 1, waves 4-7 on branch 2, in lock step.
 // For branch k in {1,2}:

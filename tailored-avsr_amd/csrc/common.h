@@ -211,8 +211,8 @@ int probe_fork(hipStream_t forked, hipStream_t caller, bool at_join);   // probe
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
-// cgmlp.hip: the summed partial slab [C][K+1] of a depthwise convolution's backward -> dw [C][K] and dbias [C] (tap K is the bias);
-// shared by tavsr_dwconv_gate_bwd and tavsr_dwconv_add_bwd
+// dwconv_time.hip: the summed partial slab [C][K+1] of a depthwise convolution's backward -> dw [C][K] and dbias [C] (tap K is the
+// bias); shared by tavsr_dwconv_gate_bwd (cgmlp.hip), tavsr_dwconv_add_bwd and tavsr_glu_dwconv_bwd
 int dwconv_split(const float* sum, float* dw, float* dbias, int C, int K, int accumulate, hipStream_t stream);
 
 }  // namespace tavsr

@@ -3,7 +3,7 @@ conformer/encoder_layer.py, espnet2/asr/encoder/conformer_encoder.py, restated f
 tests/test_conformer_host.py and tests/test_gpu_conformer.py.  The dtype follows the inputs: as ``.double()`` it is the float64
 reference, in fp32 it sets the error scale.  The attention, the feed-forward block, the embeddings and the encoder's layer loop
 (intermediate CTC taps, self-conditioning) are oracle/'s, imported; new here are the convolution module on ``nn.Conv1d``,
-``F.glu`` and ``nn.BatchNorm1d`` and the layer's sequence.  Also the GLU + depthwise convolution of csrc/conformer_conv.hip and
+``F.glu`` and ``nn.BatchNorm1d`` and the layer's sequence.  Also the GLU + depthwise convolution of csrc/dwconv_time.hip and
 its backward written out by their formulas."""
 import torch
 import torch.nn as nn

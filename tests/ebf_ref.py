@@ -3,7 +3,7 @@ the published class): the reference of tests/test_ebf_host.py and tests/test_gpu
 ``.double()`` it is the float64 reference, in fp32 it sets the error scale.  The attention, the cgMLP, the feed-forward block,
 the embeddings and the encoder's layer loop (intermediate CTC taps, self-conditioning) are oracle/'s, imported; new here are the
 layer's merge - ``merge_proj(cat + depthwise_conv_fusion(cat))`` on ``torch.nn.Conv1d(groups=2D)`` - and the optional
-feed-forward blocks.  Also the depthwise-add of csrc/dwconv_add.hip and its backward written out by their formulas."""
+feed-forward blocks.  Also the depthwise-add of csrc/dwconv_time.hip and its backward written out by their formulas."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F

@@ -1,4 +1,4 @@
-"""GPU: Conformer on the HIP path - the GLU + depthwise convolution kernel (csrc/conformer_conv.hip), the convolution module in
+"""GPU: Conformer on the HIP path - the GLU + depthwise convolution kernel (csrc/dwconv_time.hip), the convolution module in
 train and eval mode, the layer, the encoder, train-mode dropout with graph capture, and the recipe model end to end - against
 tests/conformer_ref.py in float64.
 

@@ -1,4 +1,4 @@
-"""GPU: E-Branchformer on the HIP path - the merge convolution kernel (csrc/dwconv_add.hip), the layer, the encoder, train-mode
+"""GPU: E-Branchformer on the HIP path - the merge convolution kernel (csrc/dwconv_time.hip), the layer, the encoder, train-mode
 dropout with graph capture, and the recipe model end to end - against tests/ebf_ref.py in float64.
 
 Tolerance (the convention of tests/test_gpu_rnnt.py / test_gpu_vocab.py): the same chain is evaluated by ebf_ref in fp32 on the
@@ -9,9 +9,10 @@ the embedding's convolutions).  Values are compared as max |a - b| / max |b|, gr
 errors and their ratio before it asserts.
 
 Measured on an MI355X on the commit that added the test (gpu error / e32, the worst over a case's outputs and, for the kernel, over
-the seven T; the errors themselves are 2e-8 ... 1e-6, so every bound that decided was a floor or 4 e32 with room):
-  kernel   C 128: K 1 1.26, K 3 1.42, K 31 3.58   C 192: 1.23, 1.49, 3.49   C 520: 1.10, 1.32, 2.69
-           (K = 31: u and dx, whose 31-term sums the CPU convolution adds in another order; dw / dbias stay below 2)
+the eight T; the errors themselves are 2e-8 ... 1e-6, so every bound that decided was a floor or 4 e32 with room; K = 15 and
+T = 257 measured when they were added, the other figures did not move):
+  kernel   C 128: K 1 1.26, K 3 1.42, K 15 2.58, K 31 3.58   C 192: 1.23, 1.49, 2.39, 3.49   C 520: 1.10, 1.32, 2.53, 2.69
+           (K = 15, 31: u and dx, whose 15- / 31-term sums the CPU convolution adds in another order; dw / dbias stay below 2.4)
   layer    D 64 k 3 1.35, D 64 k 31 1.29, D 96 k 3 1.29, D 96 k 31 1.25;  D 64 k 3 by (use_ffn, macaron): (F, F) 1.60, (T, F) 1.38,
            (F, T) 1.43, (T, T) 1.35
   encoder  plain 1.62, intermediate CTC with conditioning 1.43
@@ -55,7 +56,7 @@ def _nan_blocks(*numels):
 
 
 # ------------------------------------------------------------------------------------------------ 1. the kernel alone
-KERNEL_T = (1, 2, 15, 16, 17, 33, 100)
+KERNEL_T = (1, 2, 15, 16, 17, 33, 100, 257)      # 257: one step beyond the backward's time chunk of 256 (two partial slabs)
 
 
 @functools.lru_cache(maxsize=None)
@@ -71,11 +72,11 @@ def _kernel_case(C, K, T, B=3):
     return x, du, w, b, out[torch.float64], out[torch.float32]
 
 
-@pytest.mark.parametrize("K", [1, 3, 31])
+@pytest.mark.parametrize("K", [1, 3, 15, 31])
 @pytest.mark.parametrize("C", [128, 192, 520])
 def test_dwconv_add_kernel_vs_float64(C, K):
     """forward and backward at every T of KERNEL_T (T = 15 / 16: half a window of K = 31 and one more, the kernel wider than the
-    sequence; T = 100: two time tiles; C = 520: a ragged last wave), B = 3, rows strided wider than C, outputs pre-filled with
+    sequence; T = 100: two time tiles; T = 257: two backward chunks; C = 520: a ragged last wave), B = 3, rows strided wider than C, outputs pre-filled with
     NaN; dw / dbias bit-equal across two runs"""
     from tavsr import ops
     B, ld = 3, C + 8
