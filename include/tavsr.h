@@ -144,7 +144,15 @@ typedef struct tavsr_gemm_desc {
        Bit 2 (value 4) keeps the weight gradient's K slices equal (A/B aid): without it, where equal slices of whole
        lcm(H*W, 32)-pixel units leave a large part of the last round of block slots empty, the first slices are one unit
        longer than the rest (a multiple of 8 slices; the slice count, and with it tavsr_gemm_ws, depends on the bit, and
-       so does the summation order of the weight gradient - never the forward or the data gradient). */
+       so does the summation order of the weight gradient - never the forward or the data gradient).
+       Bit 4 (value 16) is no position-major bit (the field counts as zero for the above when it is the only one set): conv_mode 1
+       with b_kmajor = 0 and ldb = K: B [N][K] is FOLLOWED, at B + N * K floats, by the same weights as three bf16 planes
+       [3][N][K] (tavsr_conv_wsplit writes both).  Where the launch takes them (csrc/gemm_conv.hip, conv_x6: conv_taps 9, or
+       1 with K >= 256; B 16-byte aligned) the product runs on v_mfma_f32_32x32x16_bf16 with both operands split three ways,
+       x = h + m + l, and the six products hl, lh, mm, hm, mh, hh summed in that order into the fp32 accumulator: fp32-level
+       error (the dropped ml, lm, ll are <= 2^-23 |a b|), another rounding than the fp32 MFMA's.  NaN in gives NaN out; +-inf in
+       may give NaN (inf - inf in the split), and so may |x| > 0x1.fep127 (its high part rounds to inf).  Everywhere else the
+       bit is ignored and the fp32 B is read as before. */
   int32_t conv_mode, conv_H, conv_W, conv_C;
   const float* conv_zero;
   int32_t conv_stride, conv_taps;
@@ -1078,6 +1086,12 @@ int tavsr_fill(float* p, float value, int64_t n, tavsr_stream_t stream);
 /* data-gradient weights of a 3x3 convolution for the implicit GEMM (tavsr_gemm_desc.conv_mode 1 on dY):
  * wflip[ci][tap*Cout + co] = w2d[co][(8 - tap)*Cin + ci],  w2d = [Cout][9*Cin] */
 int tavsr_conv_wflip(const float* w2d, float* wflip, int32_t Cout, int32_t Cin, tavsr_stream_t stream);
+/* the B operand of a convolution on split operands (tavsr_gemm_desc.conv_posmajor, bit 4): w [N][K] (row stride ld floats) ->
+ * out = [N][K] fp32, a dense copy of w, followed by the planes [3][N][K] bf16 = the high, middle and low part of every weight
+ * (w = h + m + l, each rounded to nearest from what the parts before it left), the 16 k of every block permuted into the order
+ * the MFMA lanes hold them (csrc/gemm_glds.h).  K % 16 == 0, ld % 4 == 0, both pointers 16-byte aligned; out holds
+ * 5 * N * K / 2 floats. */
+int tavsr_conv_wsplit(const float* w, int64_t ld, float* out, int32_t N, int32_t K, tavsr_stream_t stream);
 int tavsr_copy2d(const float* src, int64_t lds, float* dst, int64_t ldd, int64_t M, int64_t N, tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------

@@ -155,15 +155,19 @@ template <int BM, int BN, int NT, bool BKM>
 struct SourceFor<1, false, BM, BN, NT, false, BKM> {
   using type = PairSource<ConvRowsA<BM, NT>, PlainOperand<BN, BKM, NT, true>, BM>;
 };
+template <int BM, int BN, int NT>
+struct SourceFor<1, false, BM, BN, NT, false, false, true> {      // B as bf16 planes (kConvX6)
+  using type = PairSource<ConvRowsA<BM, NT>, PlaneOperand<BN, NT>, BM>;
+};
 
 // CONV 1 + PM (3x3 / pad 1, stride 1 or 2 - conv_pm): position-major virtual rows (struct PosMajor, gemm_glds.h).  The tile's
 // tap set `taps` = OR over the positions its rows span (workgroup-uniform); the ring runs over the K-steps of these taps only,
 // in their old order: K-steps of all-padding taps are skipped.  One cursor (tap, cb) = tap and 32-channel block of the next step
-// to issue serves both operands: B is fetched at the same compacted k.
-template <int BM, int BN, int NT, bool BKM>
+// to issue serves both operands: B is fetched at the same compacted k (X6: from its bf16 planes, gemm_glds.h "split operands").
+template <int BM, int BN, int NT, bool BKM, bool X6 = false>
 struct PosMajorRowsSource : SourceDefaults {
   using R = ImageRows<BM, NT>;
-  using LB = GLoader<BN, BKM, NT>;
+  using LB = std::conditional_t<X6, PlaneLoader<BN, NT>, GLoader<BN, BKM, NT>>;
   static constexpr int kDma = R::L::NR + LB::NR;
   static constexpr bool kPosMajorRows = true;
   const TileCtx& c;
@@ -172,12 +176,13 @@ struct PosMajorRowsSource : SourceDefaults {
   int tap, cb, nk;
   bool c9;
   R rows;
-  int64_t offB[LB::NR];
+  std::conditional_t<X6, int, int64_t> offB[LB::NR];
   __device__ __forceinline__ explicit PosMajorRowsSource(const TileCtx& c_) : c(c_) {
     const tavsr_gemm_desc& d = c.d;
     const ConvGeom g(d);
     c9 = g.c9;
-    LB::offsets(d.ldb, c.n0, d.N, c.tid, offB);
+    if constexpr (X6) LB::offsets(d.K, c.n0, d.N, c.tid, offB);
+    else LB::offsets(d.ldb, c.n0, d.N, c.tid, offB);
     pm.H = g.Ho; pm.W = g.Wo;                         // the rows are output pixels (stride 1: the input map)
     pm.st = g.cs; pm.HI = d.conv_H; pm.WI = d.conv_W;
     pm.n = d.M / (g.Ho * g.Wo);
@@ -228,12 +233,17 @@ struct PosMajorRowsSource : SourceDefaults {
     cb = wrap ? 0 : cb + 1;
     tap = !wrap ? tap : up ? __builtin_ctz(up) : 9;
     rows.issue(c, c9, kk, ktap, stage);
-    LB::issue(c.B + (BKM ? (int64_t)kk * d.ldb : kk), offB, stage + BM * kBK, c.wave);
+    if constexpr (X6) LB::issue(x6_planes(d) + kk / 2, offB, stage + BM * kBK, c.wave);
+    else LB::issue(c.B + (BKM ? (int64_t)kk * d.ldb : kk), offB, stage + BM * kBK, c.wave);
   }
 };
 template <int BM, int BN, int NT, bool BKM>
 struct SourceFor<1, true, BM, BN, NT, false, BKM> {
   using type = PosMajorRowsSource<BM, BN, NT, BKM>;
+};
+template <int BM, int BN, int NT>
+struct SourceFor<1, true, BM, BN, NT, false, false, true> {
+  using type = PosMajorRowsSource<BM, BN, NT, false, true>;
 };
 
 // CONV 2 (weight gradient dW = dY^T patches): the k-major B operand is the image, B(k = m, n = tap*C + c); a 64-wide n tile lies
@@ -668,7 +678,7 @@ static int conv_wo(const tavsr_gemm_desc& d) { return (d.conv_W - 1) / std::max(
 constexpr int kPmStride2MaxPos = 36;
 static bool conv_pm(const tavsr_gemm_desc& d) {
   const bool stride_ok = d.conv_stride <= 1 || (d.conv_stride == 2 && (d.conv_posmajor & 8) && conv_ho(d) * conv_wo(d) <= kPmStride2MaxPos);
-  return d.conv_posmajor && (d.conv_mode == 1 || d.conv_mode == 2) && stride_ok && (d.conv_taps == 0 || d.conv_taps == 9) &&
+  return (d.conv_posmajor & ~kConvX6) && (d.conv_mode == 1 || d.conv_mode == 2) && stride_ok && (d.conv_taps == 0 || d.conv_taps == 9) &&
          (d.conv_mode == 2 || !d.a_rowsum);
 }
 
@@ -732,7 +742,7 @@ static void tile_order_build(const tavsr_gemm_desc& d, int BM, int nsplit, TileO
 //   weight gradient: a 128x64 tile (Cout % 128 == 0) shares one patch tile between 128 output channels: +1.6 %, and
 //     another +0.7 % with the K split re-fitted to its three block slots per CU (2304 blocks);
 //   64x64 everywhere else.  All tiles of a K slice of a weight gradient go to one XCD (zmap) where the slices are a multiple of 8.
-template <int BM, int BN, int MINW, bool AK, bool BKM, int CONV, bool PM>
+template <int BM, int BN, int MINW, bool AK, bool BKM, int CONV, bool PM, bool X6 = false, int WM = 2, int WN = 2, int S = 2>
 static int launch_conv_tile(const tavsr_gemm_desc& d, const Plan& p, hipStream_t s) {
   const int zmap = (CONV == 2 || CONV == 5 || CONV == 7) && p.nsplit >= 8 && p.nsplit % 8 == 0;
   const bool two = PM && CONV == 2;        // two slice lengths: the position-major weight gradient's alone
@@ -741,9 +751,9 @@ static int launch_conv_tile(const tavsr_gemm_desc& d, const Plan& p, hipStream_t
   if constexpr (PM && CONV == 1) {
     GemmArgsOrd ao{a, {}};
     tile_order_build(d, BM, p.nsplit, ao.ord);
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, 2, 2, 2, MINW, AK, BKM, 1, CONV, true>), grid, dim3(256), 0, s, ao);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, S, MINW, AK, BKM, 1, CONV, true, X6>), grid, dim3(WM * WN * 64), 0, s, ao);
   } else {
-    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, 2, 2, 2, MINW, AK, BKM, 1, CONV, PM>), grid, dim3(256), 0, s, a);
+    hipLaunchKernelGGL((gemm_glds_kernel<BM, BN, WM, WN, S, MINW, AK, BKM, 1, CONV, PM, X6>), grid, dim3(WM * WN * 64), 0, s, a);
   }
   TAVSR_LAUNCH_CHECK();
   return launch_epilogue(a, s);
@@ -752,15 +762,37 @@ static int launch_conv_tile(const tavsr_gemm_desc& d, const Plan& p, hipStream_t
 // conv_posmajor: honoured for the 9 padded taps at stride 1, and at stride 2 on small maps where bit 3 asks (conv_pm; ignored
 // elsewhere, include/tavsr.h): same tiles; forward / data gradient keep their K split, the weight gradient's slices are
 // whole images (plan_conv)
-template <int BM, int BN, int MINW, bool AK, bool BKM, int CONV>
+template <int BM, int BN, int MINW, bool AK, bool BKM, int CONV, bool X6 = false, int WM = 2, int WN = 2, int S = 2>
 static int launch_conv_pm(const tavsr_gemm_desc& d, const Plan& p, hipStream_t s) {
-  return conv_pm(d) ? launch_conv_tile<BM, BN, MINW, AK, BKM, CONV, true>(d, p, s) : launch_conv_tile<BM, BN, MINW, AK, BKM, CONV, false>(d, p, s);
+  return conv_pm(d) ? launch_conv_tile<BM, BN, MINW, AK, BKM, CONV, true, X6, WM, WN, S>(d, p, s)
+                    : launch_conv_tile<BM, BN, MINW, AK, BKM, CONV, false, X6, WM, WN, S>(d, p, s);
+}
+
+// conv_posmajor's bit 4 applies: forward / data gradient with both operands k-contiguous, the 9 padded taps or a 1x1 of at least
+// 256 channels (the 64- and 128-channel downsamples are 2 and 4 K-steps long and lost 10 % to the wider B stage), a dense B whose
+// planes are 16-byte chunks the LDS-DMA can address with 32-bit offsets.  A K split keeps its slices (whole K-steps).
+// Tiles (launch_conv; profiles/r14_notes.md): the split costs VALU per A sub-tile and K-step, the MFMAs of a wave grow with its
+// tile's columns, and a 64-row block re-reads the whole B for 64 rows - so, where there are tiles enough, 128x128 with 64x64 wave
+// tiles (Cout % 128 == 0) and 128x64 with four 32x64 wave tiles (Cout = 64): +7 to +18 % on every trunk row over the fp32
+// launch's 64x128 / 64x64, which stay for short launches.  A stage holds BM * 128 + BN * 192 bytes, two stages: 128x128 80 KB and
+// 128x64 56 KB (two blocks per CU), 64x128 64 KB (two), 64x64 40 KB (four).
+static bool conv_x6(const tavsr_gemm_desc& d, const Plan& p) {
+  return (d.conv_posmajor & kConvX6) && d.conv_mode == 1 && !d.a_kmajor && !d.b_kmajor && d.ldb == d.K &&
+         (d.conv_taps == 0 || d.conv_taps == 9 || (d.conv_taps == 1 && d.K >= 256)) && aligned16(d.B) && (int64_t)d.N * d.K * 6 < (1ll << 31);
 }
 
 int launch_conv(const tavsr_gemm_desc& d, const Plan& p, hipStream_t s) {
   switch (d.conv_mode) {
     case 1:       // A patches (NT / NN)
       if (d.b_kmajor) return launch_conv_pm<64, 64, 5, false, true, 1>(d, p, s);
+      if (conv_x6(d, p)) {
+        // a full round of the 128-row tiles' two block slots per CU: below it the 64-row tiles spread over more CUs
+        const bool big = p.nsplit == 1 && (int64_t)cdiv(d.M, 128) * cdiv(d.N, d.N % 128 == 0 ? 128 : 64) >= 512;
+        if (big && d.N % 128 == 0) return launch_conv_pm<128, 128, 2, false, false, 1, true>(d, p, s);
+        if (big) return launch_conv_pm<128, 64, 2, false, false, 1, true, 4, 1>(d, p, s);
+        if (p.nsplit == 1 && d.N % 128 == 0) return launch_conv_pm<64, 128, 2, false, false, 1, true>(d, p, s);
+        return launch_conv_pm<64, 64, 4, false, false, 1, true>(d, p, s);
+      }
       if (p.nsplit == 1 && d.N % 128 == 0) return launch_conv_pm<64, 128, 3, false, false, 1>(d, p, s);
       return launch_conv_pm<64, 64, 5, false, false, 1>(d, p, s);
     case 2:       // B patches (TN)

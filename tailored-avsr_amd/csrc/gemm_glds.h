@@ -360,6 +360,7 @@ static bool vec_epi_ok(const tavsr_gemm_desc& d) {
 //                           (the SOURCE address is permuted, the LDS write stays linear; ds_read_b128 applies the
 //                           same XOR: the 16 lanes of a b128 group hit 16 distinct 16-byte slots)
 //   row-contiguous operand: [k][ROWS floats], read by ds_read_b32 over 32 consecutive rows
+//   B as three bf16 planes : [plane][row][4 chunks of 8 bf16], chunk c of row r at c ^ ((r >> 2) & 3) ("split operands" below)
 typedef __attribute__((address_space(3))) float lds_float;
 typedef const __attribute__((address_space(1))) float glb_float;
 
@@ -417,6 +418,77 @@ __device__ __forceinline__ void read_frag_g(const float* __restrict__ s, int row
     const float4 v = *reinterpret_cast<const float4*>(s + row * 32 + (((2 * g + lk) ^ ((row >> 1) & 7)) << 2));
     f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w;
   }
+}
+
+// ---------------------------------------------------------------------------------------------- split operands (x6)
+// bf16 MFMA on three-way split fp32 operands (tavsr_gemm_desc.conv_posmajor, bit 4): x = h + m + l, every part a bf16 value rounded to
+// nearest from what the parts before it left (h = bf16(x), m = bf16(x - h), l = bf16(x - h - m); the subtractions are exact and
+// so is the sum for normal-range x).  A product a b is the six MFMAs hl, lh, mm, hm, mh, hh of one 16-k block, small to large
+// into the ONE fp32 accumulator; ml, lm, ll (<= 2^-23 |a b|) are dropped.  Zeros split to zeros, NaN to NaN; +-inf gives
+// inf - inf = NaN in m.
+//   A stays the fp32 image above and is split in registers: the lane's two read_frag_g chunks of a 16-k block (k-groups 2b and
+//     2b + 1: k = 16b + 4 lk + j and + 8) are the 8 values of its MFMA operand, in that order.
+//   B arrives split (tavsr_conv_wsplit): three planes [N][K] bf16 in which the 16 k of a block are stored in the order the A
+//     lanes hold them - 16-byte chunk lk of block b = k 16b + 4 lk + {0..3}, 16b + 8 + 4 lk + {0..3} - so one ds_read_b128 is a
+//     lane's operand of one plane.  LDS image: [plane][row][4 chunks] (64 bytes per row and plane), chunk c = 2b + lk of row r
+//     stored at chunk c ^ ((r >> 2) & 3) (the SOURCE address is permuted, as above): the 16 lanes of a ds_read_b128 group are
+//     rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one chunk - r & 3 picks one of 4 64-byte rows of the 256-byte bank
+//     window, (r >> 2) & 3 is different in each of the group's four quads: 16 distinct slots.
+// A k-major fragment reader can join by filling the same 8-value registers (split_frag takes them from anywhere).
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+constexpr int kX6RowFloats = 48;      // a B row of a K-step in LDS: 3 planes x 32 bf16
+
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // (bf16(a), bf16(b)) rounded to nearest even, a in the low half
+  f32x2 v = {a, b};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
+}
+__device__ __forceinline__ void split_pair(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
+  h = pk_bf16(a, b);
+  a -= __uint_as_float(h << 16);
+  b -= __uint_as_float(h & 0xffff0000u);
+  m = pk_bf16(a, b);
+  a -= __uint_as_float(m << 16);
+  b -= __uint_as_float(m & 0xffff0000u);
+  l = pk_bf16(a, b);
+}
+// the 8 fp32 values of a lane's operand of one 16-k block -> its three bf16 operands
+__device__ __forceinline__ void split_frag(const float (&f)[8], uint4& h, uint4& m, uint4& l) {
+  split_pair(f[0], f[1], h.x, m.x, l.x);
+  split_pair(f[2], f[3], h.y, m.y, l.y);
+  split_pair(f[4], f[5], h.z, m.z, l.z);
+  split_pair(f[6], f[7], h.w, m.w, l.w);
+}
+__device__ __forceinline__ f32x16 mfma_bf16(const uint4& a, const uint4& b, const f32x16& c) {
+  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// LDS-DMA of the B planes' K-step (BN rows x 3 planes x 4 chunks of 16 bytes) into the image above
+template <int ROWS, int NT>
+struct PlaneLoader {
+  static constexpr int NR = ROWS * 12 / NT;
+  static_assert(ROWS * 12 % NT == 0 && (ROWS * 4) % 64 == 0, "a wave instruction stays inside one plane");
+  // float offsets of this thread's chunks at k = 0 (planes of n rows x K bf16 each, fewer than 2^31 bytes in all)
+  __device__ static __forceinline__ void offsets(int K, int row0, int nrows, int tid, int (&off)[NR]) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i) {
+      const int q = i * NT + tid, plane = q / (ROWS * 4), r = q % (ROWS * 4);
+      const int row = r >> 2, cl = (r & 3) ^ ((row >> 2) & 3);
+      off[i] = (plane * nrows + min(row0 + row, nrows - 1)) * (K / 2) + cl * 4;
+    }
+  }
+  // gk: the planes at the K-step's k (2 bf16 per float)
+  __device__ static __forceinline__ void issue(const float* __restrict__ gk, const int (&off)[NR], float* __restrict__ img, int wave) {
+#pragma unroll
+    for (int i = 0; i < NR; ++i)
+      __builtin_amdgcn_global_load_lds((glb_float*)(gk + off[i]), (lds_float*)(img + (i * NT + wave * 64) * 4), 16, 0, 0);
+  }
+};
+// a lane's operand of plane p, row `row`, 16-k block b
+template <int ROWS>
+__device__ __forceinline__ uint4 read_plane(const float* __restrict__ s, int p, int row, int b, int lk) {
+  return *reinterpret_cast<const uint4*>(s + ((p * ROWS + row) * 4 + ((2 * b + lk) ^ ((row >> 2) & 3))) * 4);
 }
 
 template <int N>
@@ -495,6 +567,23 @@ struct PlainOperand {
   __device__ __forceinline__ void issue(int kt, float* img) { L::issue(gk + kt * kstep, off, img, c.wave); }
 };
 
+// The B operand as the three bf16 planes behind B [N][K] (kConvX6; the image is described at "split operands" above)
+constexpr int kConvX6 = 16;      // tavsr_gemm_desc.conv_posmajor, bit 4
+__device__ __forceinline__ const float* x6_planes(const tavsr_gemm_desc& d) { return d.B + (int64_t)d.N * d.K; }
+template <int ROWS, int NT>
+struct PlaneOperand {
+  using L = PlaneLoader<ROWS, NT>;
+  static constexpr int kDma = L::NR;
+  const TileCtx& c;
+  int off[L::NR];
+  const float* gk;          // the planes at k = kbeg
+  __device__ __forceinline__ explicit PlaneOperand(const TileCtx& c_) : c(c_) {
+    L::offsets(c.d.K, c.n0, c.d.N, c.tid, off);
+    gk = x6_planes(c.d) + c.kbeg / 2;
+  }
+  __device__ __forceinline__ void issue(int kt, float* img) { L::issue(gk + kt * (kBK / 2), off, img, c.wave); }
+};
+
 template <class HA, class HB, int BM>
 struct PairSource : SourceDefaults {
   static constexpr int kDma = HA::kDma + HB::kDma;
@@ -509,8 +598,8 @@ struct PairSource : SourceDefaults {
   }
 };
 
-template <int CONV, bool PM, int BM, int BN, int NT, bool AK, bool BKM>
-struct SourceFor;           // ::type, specialised next to each source
+template <int CONV, bool PM, int BM, int BN, int NT, bool AK, bool BKM, bool X6 = false>
+struct SourceFor;           // ::type, specialised next to each source (X6: B as bf16 planes, CONV 1 only)
 template <int BM, int BN, int NT, bool AK, bool BKM>
 struct SourceFor<0, false, BM, BN, NT, AK, BKM> {
   using type = PairSource<PlainOperand<BM, AK, NT, false>, PlainOperand<BN, BKM, NT, true>, BM>;
@@ -523,16 +612,19 @@ struct SourceFor<0, false, BM, BN, NT, AK, BKM> {
 // KW > 1: the k-groups of every K-step are dealt to KW wave sets (intra-block K split, summed through LDS at the end):
 // a lone 64x64 tile on a CU then runs 2 waves per SIMD with half the dependent-MFMA chain per K-step each.
 // Two slice lengths (plan_conv, gemm_conv.hip): the first n_big slices are kunit longer; n_big = 0 everywhere else.
-template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
+// X6 (CONV 1 with both operands k-contiguous): the K-step runs on bf16 MFMAs over split operands ("split operands" above); the
+// stage's B image is then the three planes (BN * 192 bytes instead of BN * 128).
+template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false, bool X6 = false>
 __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, int nsplit, int tiles_n, int bid, bool vec_epi,
                                           int zidx, int n_big = 0, int kunit = 0) {
   constexpr int BK = kBK, NG = BK / 8;
   static_assert(NG % KW == 0, "k-groups must divide over the wave sets");
   static_assert(!PM || KW == 1, "position-major order: one wave set");
+  static_assert(!X6 || (CONV == 1 && !AK && !BKM && KW == 1), "split operands: CONV 1, both operands k-contiguous, one wave set");
   constexpr int NT = WM * WN * KW * 64;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
-  using Src = typename SourceFor<CONV, PM, BM, BN, NT, AK, BKM>::type;
-  constexpr int ASZ = BM * BK, STAGE = (BM + BN) * BK;
+  using Src = typename SourceFor<CONV, PM, BM, BN, NT, AK, BKM, X6>::type;
+  constexpr int ASZ = BM * BK, STAGE = BM * BK + BN * (X6 ? kX6RowFloats : BK);
   constexpr int G = Src::kDma;                  // LDS-DMA instructions per wave per tile
   static_assert((S - 2) * G <= 63, "vmcnt field");
   __shared__ __attribute__((aligned(1024))) float smem[S * STAGE];
@@ -580,6 +672,49 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   auto compute = [&](int st) {
     const float* a_s = smem + st * STAGE;
     const float* b_s = a_s + ASZ;
+    if constexpr (X6) {
+      float af[2][TM][8];
+      uint4 bq[2][TN][3];
+      auto read_block = [&](int b, float (&fa)[TM][8], uint4 (&qb)[TN][3]) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          float lo[4], hi[4];
+          read_frag_g<BM, false>(a_s, arow + i * 32, 2 * b, lk, lo);
+          read_frag_g<BM, false>(a_s, arow + i * 32, 2 * b + 1, lk, hi);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { fa[i][e] = lo[e]; fa[i][4 + e] = hi[e]; }
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int p = 0; p < 3; ++p) qb[j][p] = read_plane<BN>(b_s, p, brow + j * 32, b, lk);
+      };
+      read_block(0, af[0], bq[0]);
+#pragma unroll
+      for (int b = 0; b < BK / 16; ++b) {
+        const int c = b & 1;
+        if (b + 1 < BK / 16) read_block(b + 1, af[c ^ 1], bq[c ^ 1]);
+        GEMM_SB();        // as below: the next block's fragment reads, then this block's split and MFMAs
+        uint4 ah[TM], am[TM], al[TM];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) split_frag(af[c][i], ah[i], am[i], al[i]);
+        // hl, lh, mm, hm, mh, hh: small to large (index 0 / 1 / 2 = h / m / l)
+#pragma unroll
+        for (int pr = 0; pr < 6; ++pr) {
+          constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+              acc[i][j] = mfma_bf16(PA[pr] == 0 ? ah[i] : PA[pr] == 1 ? am[i] : al[i], bq[c][j][PB[pr]], acc[i][j]);
+        }
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+          asum[i] += ((af[c][i][0] + af[c][i][1]) + (af[c][i][2] + af[c][i][3])) + ((af[c][i][4] + af[c][i][5]) + (af[c][i][6] + af[c][i][7]));
+        GEMM_SB();
+      }
+      return;
+    }
     float af[2][TM][4], bf[2][TN][4];
 #pragma unroll
     for (int i = 0; i < TM; ++i) read_frag_g<BM, AK>(a_s, arow + i * 32, kw, lk, af[0][i]);
@@ -725,12 +860,12 @@ struct TileMap<CONV, PM, false> {
   }
 };
 
-template <int BM, int BN, int WM, int WN, int S, int MINW, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false>
+template <int BM, int BN, int WM, int WN, int S, int MINW, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false, bool X6 = false>
 __global__ __launch_bounds__(WM* WN * KW * 64, MINW)
 void gemm_glds_kernel(const std::conditional_t<PM && CONV == 1, GemmArgsOrd, GemmArgs> xargs) {
   int bid, zidx;
   const GemmArgs& args = TileMap<CONV, PM>::map(xargs, bid, zidx);
-  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx,
+  glds_tile<BM, BN, WM, WN, S, AK, BKM, KW, CONV, PM, X6>(args.d, args.kchunk, args.nsplit, args.tiles_n, bid, args.vec_epi != 0, zidx,
                                                       args.n_big, args.kunit);
 }
 

@@ -11,6 +11,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "gemm_glds.h"      // split_frag: the weight planes are split exactly as the kernel splits its activations
 
 namespace tavsr {
 
@@ -549,6 +550,29 @@ __global__ void conv_wflip_kernel(const float* __restrict__ w2d, float* __restri
   wflip[i] = w2d[(int64_t)co * 9 * Cin + (int64_t)(8 - tap) * Cin + ci];
 }
 
+// The B operand of a split-operand convolution (tavsr_gemm_desc.conv_posmajor bit 4; gemm_glds.h "split operands"): w [N][K] (row
+// stride ld) -> its dense copy and, behind it, three bf16 planes [3][N][K], the 16 k of every block in the order the MFMA lanes hold
+// them: 16-byte chunk lk of block b = k 16b + 4 lk + {0..3}, 16b + 8 + 4 lk + {0..3}.  One thread per chunk.
+__global__ void conv_wsplit_kernel(const float* __restrict__ w, int64_t ld, float* __restrict__ out, int N, int K) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int cpr = K / 8;                    // chunks per row
+  if (i >= (int64_t)N * cpr) return;
+  const int n = (int)(i / cpr), ch = (int)(i % cpr), b = ch >> 1, lk = ch & 1;
+  const float* src = w + (int64_t)n * ld + 16 * b + 4 * lk;
+  const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 8);
+  const float f[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+  float* cp = out + (int64_t)n * K + 16 * b + 4 * lk;
+  *reinterpret_cast<float4*>(cp) = lo;
+  *reinterpret_cast<float4*>(cp + 8) = hi;
+  uint4* planes = reinterpret_cast<uint4*>(out + (int64_t)N * K);
+  uint4 h, m, l;
+  split_frag(f, h, m, l);
+  const int64_t plane = (int64_t)N * cpr;
+  planes[i] = h;
+  planes[plane + i] = m;
+  planes[2 * plane + i] = l;
+}
+
 __global__ void fill_kernel(float* __restrict__ p, float v, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -768,6 +792,15 @@ extern "C" int tavsr_copy2d(const float* src, int64_t lds, float* dst, int64_t l
 extern "C" int tavsr_conv_wflip(const float* w2d, float* wflip, int32_t Cout, int32_t Cin, tavsr_stream_t stream) {
   TAVSR_REQUIRE(w2d && wflip && Cout > 0 && Cin > 0, TAVSR_EINVAL, "conv_wflip: bad arguments");
   hipLaunchKernelGGL(conv_wflip_kernel, grid1d((int64_t)Cout * Cin * 9), dim3(256), 0, (hipStream_t)stream, w2d, wflip, Cout, Cin);
+  TAVSR_LAUNCH_CHECK();
+  return TAVSR_OK;
+}
+
+extern "C" int tavsr_conv_wsplit(const float* w, int64_t ld, float* out, int32_t N, int32_t K, tavsr_stream_t stream) {
+  TAVSR_REQUIRE(w && out && N > 0 && K > 0, TAVSR_EINVAL, "conv_wsplit: bad arguments");
+  TAVSR_REQUIRE(K % 16 == 0 && ld % 4 == 0 && ld >= K && (((uintptr_t)w | (uintptr_t)out) & 15) == 0, TAVSR_EUNSUPPORTED,
+                "conv_wsplit: K %% 16 == 0 and 16-byte aligned rows");
+  hipLaunchKernelGGL(conv_wsplit_kernel, grid1d((int64_t)N * (K / 8)), dim3(256), 0, (hipStream_t)stream, w, ld, out, N, K);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
 }

@@ -46,6 +46,11 @@ def _w2d(w):
     return ops.transpose_inner(w.contiguous(), co, ci, kh * kw).view(co, kh * kw * ci)
 
 
+def _planes(w, taps=9):
+    """the bf16 planes of a trunk convolution's GEMM weight (ops.conv_wsplit), made once per step where its launch takes them"""
+    return ops.conv_wsplit(w) if ops.x6_takes(w, taps) else None
+
+
 def _w2d_grad(g, shape):
     co, ci, kh, kw = shape
     return ops.transpose_inner(g, co, kh * kw, ci).view(shape)
@@ -141,16 +146,16 @@ class VisualFrontendFn(torch.autograd.Function):
                 w1 = _w2d(p[pre + "conv1.weight"])
                 # implicit GEMM: the image itself is the A operand (no im2col matrix), also for the stride-2 blocks
                 Ho, Wo = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-                z1 = ops.conv3x3_fwd(Xin, w1, Hin, Win, stride)
+                z1 = ops.conv3x3_fwd(Xin, w1, Hin, Win, stride, planes=_planes(w1))
                 m1, r1 = _BN.stats(z1, pre + "bn1.", bufs, training)
                 y1 = ops.bn_apply_fwd(z1, m1, r1, p[pre + "bn1.weight"], p[pre + "bn1.bias"], None, "swish")
                 w2 = _w2d(p[pre + "conv2.weight"])
-                z2 = ops.conv3x3_fwd(y1, w2, Ho, Wo)
+                z2 = ops.conv3x3_fwd(y1, w2, Ho, Wo, planes=_planes(w2))
                 m2, r2 = _BN.stats(z2, pre + "bn2.", bufs, training)
                 ds = None
                 if has_ds:
                     wd = _w2d(p[pre + "downsample.0.weight"])
-                    zd = ops.conv3x3_fwd(Xin, wd, Hin, Win, stride, taps=1)
+                    zd = ops.conv3x3_fwd(Xin, wd, Hin, Win, stride, taps=1, planes=_planes(wd, 1))
                     md, rd = _BN.stats(zd, pre + "downsample.1.", bufs, training)
                     res = ops.bn_apply_fwd(zd, md, rd, p[pre + "downsample.1.weight"], p[pre + "downsample.1.bias"], None, None)
                     ds = (zd, md, rd, wd)
@@ -200,14 +205,16 @@ class VisualFrontendFn(torch.autograd.Function):
             dres, dz2, G[pre + "bn2.weight"], G[pre + "bn2.bias"] = ops.bn_bwd(
                 d, z2, m2, r2, p[pre + "bn2.weight"], p[pre + "bn2.bias"], res, "swish")
             wgrad(pre + "conv2.weight", lambda: _w2d_grad(_conv3x3_dw(dz2, y1, N, Ho, Wo, planes), p[pre + "conv2.weight"].shape))
-            dy1 = ops.conv3x3_dx(dz2, ops.conv_wflip(w2, planes, planes), Ho, Wo)
+            wf2 = ops.conv_wflip(w2, planes, planes)
+            dy1 = ops.conv3x3_dx(dz2, wf2, Ho, Wo, planes=_planes(wf2))
             _, dz1, G[pre + "bn1.weight"], G[pre + "bn1.bias"] = ops.bn_bwd(
                 dy1, z1, m1, r1, p[pre + "bn1.weight"], p[pre + "bn1.bias"], None, "swish", need_dz=False)
             fused_ds = False
             if stride == 1:
                 wgrad(pre + "conv1.weight", lambda: _w2d_grad(_conv3x3_dw(dz1, Xin, N, Hin, Win, cin), p[pre + "conv1.weight"].shape))
                 # identity skip: its gradient joins in the GEMM epilogue (no separate add over the 0.4 GB maps)
-                dX = ops.conv3x3_dx(dz1, ops.conv_wflip(w1, planes, cin), Hin, Win, res=None if ds is not None else dres)
+                wf1 = ops.conv_wflip(w1, planes, cin)
+                dX = ops.conv3x3_dx(dz1, wf1, Hin, Win, res=None if ds is not None else dres, planes=_planes(wf1))
             else:
                 wgrad(pre + "conv1.weight", lambda: _w2d_grad(_conv3x3_dw(dz1, Xin, N, Hin, Win, cin, stride), p[pre + "conv1.weight"].shape))
                 dcol1 = ops.linear_dx(dz1, w1)

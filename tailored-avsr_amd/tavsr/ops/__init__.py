@@ -88,6 +88,11 @@ CONV_DW_UNEVEN = os.environ.get("TAVSR_CONV_DW_UNEVEN", "1") != "0"
 CONV_TAPSKIP_STRIDE2 = os.environ.get("TAVSR_CONV_TAPSKIP_STRIDE2", "1") != "0"
 CONV_TAPSKIP_STRIDE2_DW = os.environ.get("TAVSR_CONV_TAPSKIP_STRIDE2_DW", "0") != "0"
 CONV_TAPSKIP_STRIDE2_MAXPOS = 36
+# Forward and data gradient of the trunk's 3x3 / 1x1 convolutions on bf16 MFMA over three-way split fp32 operands
+# (bit 4 of tavsr_gemm_desc.conv_posmajor, csrc/gemm_glds.h "split operands"): six bf16 products per fp32 product, fp32-level error, another
+# rounding than the fp32 MFMA's.  The weights are split once per step (ops.conv_wsplit), the activations in the kernel.
+# TAVSR_CONV_X6=0: the fp32 launches, bit-identical to what they were (A/B switch).
+CONV_X6 = os.environ.get("TAVSR_CONV_X6", "1") != "0"
 
 # ---------------------------------------------------------------------------------------------- losses
 CTC_ALIGN_CHUNK = 16      # frames of emissions the alignment kernel gathers into LDS at a time (kAlignChunk, csrc/ctc.hip)

@@ -13,7 +13,7 @@ from .matmul import gemm
 __all__ = ["conv1_fwd", "conv1_bwd", "im2col3x3s2", "col2im3x3s2_relu", "conv_out", "im2col2d", "col2im2d", "stem_implicit_ok",
            "stem_pad16_ok", "stem_pad", "stem_weight_288", "stem_weight_grad_from_288", "stem_conv_fwd_pad16", "stem_conv_dw_pad16",
            "stem_conv_fwd", "stem_conv_dw", "im2col_stem", "bn_stats", "rsqrt_eps", "bn_apply_fwd", "bn_bwd", "bn_bwd_pooled",
-           "maxpool3x3s2_fwd", "bn_act_maxpool3x3s2_fwd", "maxpool3x3s2_bwd", "avgpool_fwd", "avgpool_bwd", "conv_wflip", "_tapskip",
+           "maxpool3x3s2_fwd", "bn_act_maxpool3x3s2_fwd", "maxpool3x3s2_bwd", "avgpool_fwd", "avgpool_bwd", "conv_wflip", "conv_wsplit", "x6_takes", "_tapskip",
            "_tapskip2", "_tapskip_any", "conv3x3_fwd", "conv3x3_dx", "conv3x3_dw"]
 
 
@@ -248,6 +248,32 @@ def conv_wflip(w2d, cout, cin):
     return out
 
 
+def conv_wsplit(w):
+    """the B operand of a split-operand convolution (tavsr_conv_wsplit): w [N, K] fp32 -> one buffer of 5 N K / 2 floats: the dense
+    copy of w, then its three bf16 planes [3, N, K] (high, middle and low part of every weight, k permuted inside 16-blocks as
+    the kernel reads it)."""
+    require_cuda(w)
+    N, K = w.shape
+    assert w.stride(1) == 1 and K % 16 == 0
+    out = empty(5 * N * K // 2, like=w)
+    check(lib().tavsr_conv_wsplit(ptr(w), w.stride(0), ptr(out), N, K, stream()), "tavsr_conv_wsplit")
+    return out
+
+
+def x6_takes(w, taps=9, pad0=False):
+    """does the split-operand kernel take a forward / data-gradient launch with the GEMM weight ``w`` (csrc/gemm_conv.hip, conv_x6:
+    the padded 3x3, or a 1x1 of at least 256 channels)?  False where ops.CONV_X6 is off."""
+    return bool(ops.CONV_X6 and not pad0 and w.stride(1) == 1 and w.shape[1] % 32 == 0 and (taps == 9 or w.shape[1] >= 256))
+
+
+def _x6(w, planes, taps=9, pad0=False):
+    """(B operand, conv_posmajor bit) of a forward / data-gradient launch: the caller's conv_wsplit buffer, or one made here, with
+    bit 4; (w, 0) where the launch is not one the split-operand kernel takes"""
+    if not x6_takes(w, taps, pad0):
+        return w, 0
+    return (conv_wsplit(w) if planes is None else planes), 16
+
+
 def _tapskip_bits():
     return 1 | (0 if ops.CONV_TILEORDER else 2) | (0 if ops.CONV_DW_UNEVEN else 4)
 
@@ -267,9 +293,10 @@ def _tapskip_any(H, W, stride, taps, pad0, dw=False):
     return _tapskip2(H, W, dw) if stride == 2 and taps == 9 and not pad0 else _tapskip(H, W, stride, taps, pad0, dw)
 
 
-def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None):
+def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None, planes=None):
     """implicit 3x3/p1 (taps 9) or 1x1/p0 (taps 1) convolution with stride: x [images*H*W, Cin] channels-last image rows,
-    w2d [Cout, taps*Cin] -> [images*Ho*Wo, Cout].  ``pad0``: the 3x3 window without padding (Conv2dSubsampling)."""
+    w2d [Cout, taps*Cin] -> [images*Ho*Wo, Cout].  ``pad0``: the 3x3 window without padding (Conv2dSubsampling).
+    ``planes``: conv_wsplit(w2d), where the caller has it (ops.CONV_X6; made here otherwise)."""
     M, cin = x.shape
     cout = w2d.shape[0]
     if pad0:
@@ -279,18 +306,20 @@ def conv3x3_fwd(x, w2d, H, W, stride=1, taps=9, pad0=False, bias=None, act=None)
         Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     Mo = M // (H * W) * Ho * Wo
     z = empty(Mo, cout, like=x)
-    gemm(Mo, cout, taps * cin, x, cin, w2d, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0)),
+    B, x6 = _x6(w2d, planes, taps, pad0)
+    gemm(Mo, cout, taps * cin, x, cin, B, taps * cin, z, cout, conv=(1, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0) | x6),
          bias=bias, act=act)
     return z
 
 
-def conv3x3_dx(dz, wflip, H, W, res=None):
+def conv3x3_dx(dz, wflip, H, W, res=None, planes=None):
     """data gradient: dz [pixels, Cout], wflip [Cin, 9*Cout] (conv_wflip) -> [pixels, Cin] (+ res: the skip path's
-    gradient, added in the GEMM epilogue)."""
+    gradient, added in the GEMM epilogue).  ``planes``: conv_wsplit(wflip), where the caller has it."""
     M, cout = dz.shape
     cin = wflip.shape[0]
     dx = empty(M, cin, like=dz)
-    gemm(M, cin, 9 * cout, dz, cout, wflip, 9 * cout, dx, cin, conv=(1, H, W, cout, 0, 0, _tapskip(H, W)), R=res, ldr=0 if res is None else cin)
+    B, x6 = _x6(wflip, planes)
+    gemm(M, cin, 9 * cout, dz, cout, B, 9 * cout, dx, cin, conv=(1, H, W, cout, 0, 0, _tapskip(H, W) | x6), R=res, ldr=0 if res is None else cin)
     return dx
 
 
