@@ -1347,6 +1347,34 @@ int tavsr_adam_step(float* p, const float* g, float* m, float* v, int64_t n, flo
 int tavsr_adamw_step(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                      float weight_decay, int64_t step, float grad_scale, tavsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Gradient clipping by the total norm (training_settings.grad_clip; torch.nn.utils.clip_grad_norm_ and espnet's rule
+ * "a non-finite norm skips the update"), three launches and no host read between them:
+ *   tavsr_grad_norm_parts  one partial per workgroup over n floats at g (16-byte aligned) into parts[part0 ..
+ *                          part0 + tavsr_grad_norm_nparts(n)): norm_type 2 -> sum of squares, 0 -> max |g| (infinity norm;
+ *                          a NaN anywhere gives a NaN partial).  Squares, sums and maxima are doubles.  The grid and each
+ *                          workgroup's contiguous range follow from n alone and every reduction has one fixed order (no
+ *                          atomics): the same values give the same bits at any address, on any run and on any rank.  A
+ *                          workgroup reads tavsr_grad_norm_tile() floats per pass; a range longer than tavsr_grad_norm_span()
+ *                          floats gives every workgroup several passes.  Called once per run of live gradients, into
+ *                          consecutive slots of one buffer.
+ *   tavsr_grad_clip_coef   one workgroup joins parts[0 .. nparts) in a fixed order and writes out[0] = norm (fp32),
+ *                          out[1] = coef = min(1, max_norm / (norm + 1e-6)) in fp32 as torch evaluates it on an fp32 tensor
+ *                          (reciprocal, then times max_norm), out[2] = 1 when the norm is NaN or Inf (coef is then 0), else 0;
+ *                          counters[0] += 1, counters[1] += non-finite, counters[2] += (coef < 1).
+ *   tavsr_adamw_step_clip  tavsr_adamw_step on the gradient fl(g * clip[1]) (`clip` = the `out` above, read on the device; the
+ *                          product is rounded to fp32 before grad_scale and the update see it); writes nothing when
+ *                          clip[2] != 0.  Equals scaling the buffer g by coef in fp32 and calling tavsr_adamw_step, bit for bit.
+ * ------------------------------------------------------------------------------------------- */
+int64_t tavsr_grad_norm_tile(void);
+int64_t tavsr_grad_norm_span(void);
+int32_t tavsr_grad_norm_nparts(int64_t n);
+int tavsr_grad_norm_parts(const float* g, int64_t n, int32_t norm_type, double* parts, int32_t part0, tavsr_stream_t stream);
+int tavsr_grad_clip_coef(const double* parts, int32_t nparts, int32_t norm_type, float max_norm, float* out, int32_t* counters,
+                         tavsr_stream_t stream);
+int tavsr_adamw_step_clip(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
+                          float weight_decay, int64_t step, float grad_scale, const float* clip, tavsr_stream_t stream);
+
 /* Gradient buckets of the data-parallel exchange (tavsr/dp.py): tensor t = n[t] floats at ptrs[t], its slot in
  * the flat bucket starts at off[t].  to_flat != 0: flat <- tensors (pack before the all-reduce); else tensors <-
  * scale * flat (unpack, scale = 1 / world_size).  ptrs / off / n are DEVICE arrays; max_n = max n[t] sizes the grid. */

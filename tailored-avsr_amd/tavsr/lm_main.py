@@ -76,10 +76,17 @@ def main(argv=None):
         print("\nTRAINING PHASE\n")
         os.makedirs(args.output_dir, exist_ok=True)
         val_stats = []
+        grad_clip = float(conf.training_settings.get("grad_clip", -1.0))
+        grad_clip_type = float(conf.training_settings.get("grad_clip_type", 2.0))
         for epoch in range(1, conf.epochs + 1):
-            train_loss = lm_training(lm, train_loader, optimizer, scheduler, conf.accum_grad, device)
+            train_loss = lm_training(lm, train_loader, optimizer, scheduler, conf.accum_grad, device, grad_clip=grad_clip,
+                                     grad_clip_type=grad_clip_type)
             val_loss, test_loss = lm_validation(lm, val_loader, device), lm_validation(lm, test_loader, device)
             print(f"Epoch {epoch}: TRAIN LOSS={train_loss} || VAL LOSS={val_loss} || TEST LOSS={test_loss}")
+            if grad_clip > 0 and hasattr(optimizer, "clip_stats"):
+                st = optimizer.clip_stats()
+                print(f"Epoch {epoch}: GRAD CLIP={grad_clip} || STEPS={st['steps']} || SKIPPED={st['skipped']} || "
+                      f"CLIPPED={st['clipped']} || LAST NORM={st['last_norm']}")
             val_stats.append((save_model(args.output_dir, lm, str(epoch).zfill(3)), val_loss))
         save_val_stats(args.output_dir, val_stats)
         best = [path for path, _ in sorted(val_stats, key=lambda s: s[1])[: conf.average_epochs]]

@@ -6,12 +6,19 @@
   HIP kernel over flat fp32 buffers instead of ~700 small tensor updates: parameters are re-homed as views of one flat
   buffer, gradients are packed next to them and ``tavsr_adam_step`` updates everything in one pass.
 * ``training`` / ``validation`` reproduce the reference's semantics: loss / accum_grad, optimizer step every
-  ``accum_grad`` micro-batches and at the end of the loader, no gradient clipping, returned epoch loss
+  ``accum_grad`` micro-batches and at the end of the loader, returned epoch loss
   ``sum(loss_i) / (len(loader) / accum_grad)`` (Q10).  Losses are summed on the device: one host sync per epoch
   instead of one ``.item()`` per micro-batch.
+* ``grad_clip`` (``training_settings.grad_clip``, which the reference's loop carries and never reads - SURVEY Q9 - and
+  which is off, -1.0, in every recipe) is honoured the way espnet's trainer does it: the gradient is scaled down to a total
+  norm of ``grad_clip``, and a step whose norm is NaN or Inf updates nothing and counts nowhere.  ``FusedAdam`` takes
+  the norm and applies the coefficient on the device (``set_grad_clip``) and learns of a skipped step one step late;
+  any other optimizer goes through ``torch.nn.utils.clip_grad_norm_``.
 """
 from __future__ import annotations
 
+import math
+import warnings
 from typing import Iterable, List, Optional
 
 import torch
@@ -51,10 +58,66 @@ class FusedAdam:
         self.defaults = dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay)
         self._step = 0
         self._steps = [0] * len(self.params)      # per-parameter step counts (torch.optim.Adam keeps one per parameter)
+        self._clip = None                         # (max_norm, norm_type code of the C ABI) while clipping is on
+        self._clip_dev = None                     # device / pinned buffers of the clipped step, made by set_grad_clip
+        self._clip_pending = None                 # (live parameters) of the launched step the host has not heard about yet
+        self._clip_last = None                    # (norm, coef, non-finite) of the last settled step
+        self._skip_listeners = []                 # called when a settled step turns out skipped (NoamScheduler's count)
 
     def zero_grad(self, set_to_none: bool = True):
         for p in self.params:
             p.grad = None
+
+    # ------------------------------------------------------------------------------------------ gradient clipping
+    def set_grad_clip(self, max_norm: float, norm_type: float = 2.0):
+        """Clip the total gradient norm (2-norm, or ``float("inf")`` for the largest magnitude) to ``max_norm`` in every
+        following ``step()``, torch.nn.utils.clip_grad_norm_'s arithmetic, and skip a step whose norm is NaN or Inf the way
+        espnet's trainer does: no parameter, no moment and no step count changes.  ``max_norm <= 0`` turns it off again
+        (``step()`` then launches exactly what it launches without this call).
+
+        Nothing is read back between the norm and the update: the device decides, and the host hears of a skipped step when
+        it settles that step (``sync_clip``) - at the next ``step()``, in ``state_dict()`` / ``clip_stats()``, or when the
+        trainer ends its epoch - and then takes back the step counts it had advanced."""
+        norm_type = float(norm_type)
+        if norm_type not in (2.0, math.inf):
+            raise ValueError(f"norm_type must be 2.0 or float('inf'), got {norm_type}")
+        self.sync_clip()
+        if max_norm is None or max_norm <= 0:
+            self._clip = None
+            return
+        self._clip = (float(max_norm), 2 if norm_type == 2.0 else 0)
+        if self._clip_dev is None:
+            dev, lib = self.flat.device, L.lib()
+            ends = self.offsets[1:] + [self.flat.numel()]
+            # one slot per workgroup of every norm launch; parameter by parameter is the most any split into runs can take
+            nparts = sum(lib.tavsr_grad_norm_nparts(e - o) for o, e in zip(self.offsets, ends))
+            self._clip_dev = dict(parts=torch.zeros(nparts, dtype=torch.float64, device=dev),
+                                  out=torch.zeros(3, dtype=torch.float32, device=dev),
+                                  counters=torch.zeros(3, dtype=torch.int32, device=dev),
+                                  host=torch.zeros(3, dtype=torch.float32).pin_memory(), event=torch.cuda.Event())
+
+    def sync_clip(self) -> bool:
+        """Settle the clipped step that is still in flight, if any: wait for ITS event (never for the stream or the device),
+        and if its norm was not finite take back the counts ``step()`` advanced for it.  True when that step was skipped."""
+        live, self._clip_pending = self._clip_pending, None
+        if live is None:
+            return False
+        self._clip_dev["event"].synchronize()
+        self._clip_last = tuple(self._clip_dev["host"].tolist())
+        if self._clip_last[2] == 0.0:
+            return False
+        for i in live:
+            self._steps[i] -= 1
+        self._step -= 1
+        for undo in self._skip_listeners:
+            undo()
+        return True
+
+    def clip_stats(self):
+        """steps seen, steps skipped as non-finite, steps whose gradient was scaled down, and the last step's norm"""
+        self.sync_clip()
+        steps, skipped, clipped = self._clip_dev["counters"].tolist() if self._clip_dev is not None else (0, 0, 0)
+        return dict(steps=steps, skipped=skipped, clipped=clipped, last_norm=self._clip_last[0] if self._clip_last else None)
 
     @torch.no_grad()
     def step(self, grad_scale: float = 1.0):
@@ -66,8 +129,17 @@ class FusedAdam:
         Under data parallelism ``GradBuckets.allreduce_mean`` replaces a missing gradient by zeros before the exchange (a
         layer skipped by stochastic depth on this rank may have run on another), so there every parameter is stepped every
         time - moment decay, decoupled weight decay and step count included - exactly as torch DDP + torch.optim.Adam
-        behave; a single-process run skips such a parameter.  The shipped recipes set the skip rates to 0."""
+        behave; a single-process run skips such a parameter.  The shipped recipes set the skip rates to 0.
+
+        With ``set_grad_clip`` on, three kinds of launch follow the pack: the norm's partial sums over the same runs (the
+        gradient slot of a parameter without a gradient holds an earlier step's values and must stay out of the norm, as
+        torch's clip_grad_norm_ only sees parameters that have one), the one-workgroup finalize, and the update with the
+        coefficient folded in.  The three floats it decided on travel to a pinned host slot behind the update."""
         from . import ops
+        if self._clip is not None:
+            if grad_scale != 1.0:
+                raise ValueError("grad_scale and set_grad_clip do not combine: the norm is taken over the packed gradient")
+            self.sync_clip()            # the previous step's verdict, before this step's counts and bias corrections
         g = self.param_groups[0]
         live = [i for i, p in enumerate(self.params) if p.grad is not None]
         dst = [self.grad[self.offsets[i]: self.offsets[i] + self.params[i].numel()] for i in live]
@@ -84,19 +156,45 @@ class FusedAdam:
                 b += 1
             runs.append((live[a], live[b]))
             k = b + 1
-        for ia, ib in runs:
-            lo = self.offsets[ia]
-            hi = self.offsets[ib + 1] if ib + 1 < len(self.params) else self.flat.numel()
+        spans = [(self.offsets[ia], self.offsets[ib + 1] if ib + 1 < len(self.params) else self.flat.numel(), self._steps[ia])
+                 for ia, ib in runs]
+        if self._clip is not None:
+            return self._clipped_update(g, live, spans)
+        for lo, hi, count in spans:
             L.check(L.lib().tavsr_adamw_step(L.addr(self.flat, lo), L.addr(self.grad, lo), L.addr(self.exp_avg, lo),
                                              L.addr(self.exp_avg_sq, lo), hi - lo, g["lr"], g["betas"][0], g["betas"][1],
-                                             g["eps"], g.get("weight_decay", 0.0), self._steps[ia], grad_scale, L.stream()),
+                                             g["eps"], g.get("weight_decay", 0.0), count, grad_scale, L.stream()),
                     "tavsr_adamw_step")
 
+    def _clipped_update(self, g, live, spans):
+        lib, d = L.lib(), self._clip_dev
+        max_norm, norm_type = self._clip
+        part0 = 0
+        for lo, hi, _ in spans:
+            k = lib.tavsr_grad_norm_nparts(hi - lo)
+            if part0 + k > d["parts"].numel():
+                raise L.TavsrError(f"gradient norm: {part0 + k} partials for {d['parts'].numel()} slots")
+            L.check(lib.tavsr_grad_norm_parts(L.addr(self.grad, lo), hi - lo, norm_type, L.ptr(d["parts"]), part0, L.stream()),
+                    "tavsr_grad_norm_parts")
+            part0 += k
+        L.check(lib.tavsr_grad_clip_coef(L.ptr(d["parts"]), part0, norm_type, max_norm, L.ptr(d["out"]), L.ptr(d["counters"]),
+                                         L.stream()), "tavsr_grad_clip_coef")
+        for lo, hi, count in spans:
+            L.check(lib.tavsr_adamw_step_clip(L.addr(self.flat, lo), L.addr(self.grad, lo), L.addr(self.exp_avg, lo),
+                                              L.addr(self.exp_avg_sq, lo), hi - lo, g["lr"], g["betas"][0], g["betas"][1],
+                                              g["eps"], g.get("weight_decay", 0.0), count, 1.0, L.ptr(d["out"]), L.stream()),
+                    "tavsr_adamw_step_clip")
+        d["host"].copy_(d["out"], non_blocking=True)
+        d["event"].record()
+        self._clip_pending = live
+
     def state_dict(self):
+        self.sync_clip()                # a skipped last step must not be saved as taken
         return dict(step=self._step, steps=list(self._steps), exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, param_groups=[
             {k: v for k, v in self.param_groups[0].items() if k != "params"}])
 
     def load_state_dict(self, sd):
+        self.sync_clip()
         self._step = sd["step"]
         steps = list(sd.get("steps", [sd["step"]] * len(self.params)))
         if len(steps) != len(self.params):
@@ -125,7 +223,24 @@ class NoamScheduler(object):
     def param_groups(self):
         return self.optimizer.param_groups
 
+    def set_grad_clip(self, max_norm, norm_type=2.0):
+        """forwarded to the wrapped ``FusedAdam``; a step it later finds skipped (non-finite norm) gives its Noam count back"""
+        self.optimizer.set_grad_clip(max_norm, norm_type)
+        if self._unstep not in self.optimizer._skip_listeners:
+            self.optimizer._skip_listeners.append(self._unstep)
+
+    def _unstep(self):
+        self._step -= 1
+
+    def sync_clip(self):
+        sync = getattr(self.optimizer, "sync_clip", None)
+        return sync() if sync is not None else False
+
+    def clip_stats(self):
+        return self.optimizer.clip_stats()
+
     def step(self):
+        self.sync_clip()                # a skipped previous step returns its count before this step's rate is taken
         self._step += 1
         rate = self.rate()
         for p in self.optimizer.param_groups:
@@ -142,6 +257,7 @@ class NoamScheduler(object):
         self.optimizer.zero_grad()
 
     def state_dict(self):
+        self.sync_clip()
         return {"_step": self._step, "warmup": self.warmup, "factor": self.factor, "model_size": self.model_size,
                 "_rate": self._rate, "optimizer": self.optimizer.state_dict()}
 
@@ -259,11 +375,73 @@ def _to_device(batch, device):
     return {k: v.to(device=device, non_blocking=True) if hasattr(v, "to") else v for k, v in batch.items()}
 
 
-def training(e2e, train_loader, optimizer, scheduler, accum_grad, device="cuda", buckets: Optional[dp.GradBuckets] = None):
+class _Stepper:
+    """``optimizer.step(); scheduler.step()`` of the two training loops under ``grad_clip`` (espnet's trainer: clip the total
+    norm, and on a NaN / Inf norm take neither step).  ``grad_clip <= 0``: exactly those two calls.
+
+    * A ``FusedAdam``, bare or under ``NoamScheduler``, clips and skips on the device (``set_grad_clip``) and the host
+      learns of a skip one step late.  An external scheduler must not spend a position on a skipped step, so its
+      ``step()`` for optimizer step k is MOVED behind the settlement of step k: it is taken right before optimizer step
+      k + 1 (its learning rate is in place in time), or in ``finish()`` at the end of the epoch.
+    * Any other optimizer: ``torch.nn.utils.clip_grad_norm_`` over its ``param_groups``, ``torch.isfinite`` on the norm,
+      one warning per epoch with the number of skipped steps."""
+
+    def __init__(self, optimizer, scheduler, grad_clip, grad_clip_type):
+        self.optimizer, self.scheduler = optimizer, scheduler
+        self.grad_clip, self.norm_type = float(grad_clip), float(grad_clip_type)
+        if self.norm_type not in (2.0, math.inf):
+            raise ValueError(f"grad_clip_type must be 2.0 or float('inf'), got {grad_clip_type}")
+        inner = optimizer.optimizer if isinstance(optimizer, NoamScheduler) else optimizer
+        self.fused = inner if isinstance(inner, FusedAdam) else None
+        if self.fused is not None:
+            optimizer.set_grad_clip(self.grad_clip, self.norm_type)
+        self.clipping = self.grad_clip > 0
+        self.scheduler_due = False      # (fused, clipping) the scheduler step of the last optimizer step is still owed
+        self.steps = self.skipped = 0
+
+    def _settle(self):
+        skipped = self.fused.sync_clip()
+        if self.scheduler_due and not skipped:
+            self.scheduler.step()
+        self.scheduler_due = False
+
+    def step(self):
+        if not self.clipping:
+            self.optimizer.step()
+            if self.scheduler is not None:
+                self.scheduler.step()
+        elif self.fused is not None:
+            self._settle()
+            self.optimizer.step()
+            self.scheduler_due = self.scheduler is not None
+        else:
+            params = [p for group in self.optimizer.param_groups for p in group["params"]]
+            norm = torch.nn.utils.clip_grad_norm_(params, self.grad_clip, norm_type=self.norm_type)
+            self.steps += 1
+            if not torch.isfinite(norm):
+                self.skipped += 1
+                return
+            self.optimizer.step()
+            if self.scheduler is not None:
+                self.scheduler.step()
+
+    def finish(self):
+        if self.clipping and self.fused is not None:
+            self._settle()
+        if self.skipped:
+            warnings.warn(f"{self.skipped} of {self.steps} optimizer steps of this epoch were skipped: the gradient norm was "
+                          f"not finite")
+
+
+def training(e2e, train_loader, optimizer, scheduler, accum_grad, device="cuda", buckets: Optional[dp.GradBuckets] = None,
+             grad_clip=-1.0, grad_clip_type=2.0):
     """One epoch (avsr_main.py:27-58).  ``buckets`` (tavsr.dp.GradBuckets) adds the data-parallel gradient average
-    right before each optimizer step - the only collective on the path."""
+    right before each optimizer step - the only collective on the path.  ``grad_clip`` > 0 clips the total gradient norm
+    (``grad_clip_type`` 2.0 or ``float("inf")``) and skips non-finite steps (``_Stepper``); under data parallelism the norm is
+    taken after the average, on identical bits on every rank, so all ranks decide alike and nothing more is exchanged."""
     e2e.train()
     total = None
+    stepper = _Stepper(optimizer, scheduler, grad_clip, grad_clip_type)
     optimizer.zero_grad()
     n = len(train_loader)
     if buckets is not None:
@@ -280,12 +458,11 @@ def training(e2e, train_loader, optimizer, scheduler, accum_grad, device="cuda",
         if stepping:
             if buckets is not None:
                 buckets.allreduce_mean()
-            optimizer.step()
-            if scheduler is not None:
-                scheduler.step()
+            stepper.step()
             optimizer.zero_grad()
         d = loss.detach().reshape(())
         total = d if total is None else total + d
+    stepper.finish()
     return float(total) / (n / accum_grad)
 
 
@@ -302,11 +479,13 @@ def validation(e2e, data_loader, device="cuda"):
     return round(data_loss / len(data_loader), 3), round(data_cer / len(data_loader), 3)
 
 
-def lm_training(lm, train_loader, optimizer, scheduler, accum_grad, device="cuda"):
+def lm_training(lm, train_loader, optimizer, scheduler, accum_grad, device="cuda", grad_clip=-1.0, grad_clip_type=2.0):
     """One epoch of language-model training (lm_main.py:22-43).  Batches are tuples (token ids, lengths, ...); the optimizer
-    steps every ``accum_grad`` batches and after the last one, and the loss stays on the device until the epoch ends."""
+    steps every ``accum_grad`` batches and after the last one, and the loss stays on the device until the epoch ends.
+    ``grad_clip`` / ``grad_clip_type`` as in ``training``."""
     lm.train()
     total = None
+    stepper = _Stepper(optimizer, scheduler, grad_clip, grad_clip_type)
     optimizer.zero_grad()
     n = len(train_loader)
     for batch_idx, batch in enumerate(train_loader):
@@ -314,12 +493,11 @@ def lm_training(lm, train_loader, optimizer, scheduler, accum_grad, device="cuda
         loss = lm(xs_pad, ilens)[0] / accum_grad
         loss.backward()
         if ((batch_idx + 1) % accum_grad == 0) or (batch_idx + 1 == n):
-            optimizer.step()
-            if scheduler is not None:
-                scheduler.step()
+            stepper.step()
             optimizer.zero_grad()
         d = loss.detach().reshape(())
         total = d if total is None else total + d
+    stepper.finish()
     return float(total) / (n / accum_grad)
 
 
