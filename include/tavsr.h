@@ -1468,6 +1468,51 @@ int64_t tavsr_resample_len(int64_t n_in, double factor);
 int tavsr_resample_sinc(const float* x, int64_t n_in, float* y, int64_t n_out, double factor, double rolloff, int32_t zeros, double beta,
                         tavsr_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Fastformer additive attention (csrc/fastattn.hip; espnet2 asr/layers/fastformer.py FastSelfAttention, the `fast_selfattn`
+ * option of src/encoder/branchformer/encoder.py:106-120,223-259) between the q | k projection GEMM and the `transform` GEMM.
+ * Rows are [B*T][ld] (row b*T + t), lens [B] int64 on the device (NULL: every frame valid), dh = D / H.
+ *   tavsr_fastattn_pool: s[b,h,t] = (<W[h,:], x[b,t,:] * cs[b,:]> + bias[h]) / sqrt(dh) over ALL D columns (cs [B][D] or NULL = 1),
+ *       w_out[b,h,:] = softmax of s over t < lens[b] (two passes, fp32), exactly 0 at t >= lens[b], written for every t < T;
+ *       pooled[b,c] = sum_{t < lens[b]} w_out[b,c/dh,t] * x[b,t,c] * cs[b,c].  score_ws: B*H*T floats.  Two launches.
+ *       Frames t >= lens[b] are never read.  Called on the query rows (alpha, pq) and on the key rows with cs = pq (beta, pk).
+ *   tavsr_fastattn_scale_rows: wv[b,t,:] = pk[b,:] * q[b,t,:] on every row, wv contiguous [B*T][D].
+ *   tavsr_fastattn_bwd_pool: dpk[b,c] = sum_{t < T} dwv[b,t,c] * q[b,t,c]; a frame t >= lens[b] is read only where dwv there is
+ *       not exactly 0 (the reference sums every row: its output rows transform(pk * q) + q exist at padded frames).
+ *   tavsr_fastattn_bwd_rows: the mirror of one tavsr_fastattn_pool call.  With xs = x * cs, for t < lens[b]:
+ *       da[h] = <dpool, xs>_head h, ds[h] = w_pool[b,h,t] * (da[h] - <dpool, pool>_head h) / sqrt(dh),
+ *       g[c] = w_pool[b,c/dh,t] * dpool[b,c] + sum_h ds[h] * W[h,c];
+ *       is_k != 0: dx = g * cs (0 at t >= lens[b]), dcs[b,c] = sum_t g[c] * x[b,t,c];
+ *       is_k == 0: dx = dres + dwv * pk + g (dres + dwv * pk at t >= lens[b]); cs, dcs unused, dres / dwv / pk required.
+ *       dWb = dW [H][D] | db [H] with dW[h,c] = sum_{b,t} ds[h] * xs[c], db[h] = sum_{b,t} ds[h] (zero up to rounding: softmax
+ *       shift invariance; computed, not assumed).  dpool is the gradient of `pool` (the pooled vector BEFORE its dropout).
+ *       Per-block partial slabs in ws (>= tavsr_fastattn_bwd_ws floats), summed in a fixed order: no atomics, same bits every run.
+ * Range (tavsr_fastattn_ok): 1 <= H <= 8, D <= 512, D % H == 0, dh % 4 == 0; row strides multiples of 4 floats, 16-byte aligned
+ * rows (TAVSR_EALIGN otherwise); 1 <= B <= 65535, B * T < 2^31.  Outside it the entries return TAVSR_EUNSUPPORTED before any launch.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_fastattn_ok(int32_t D, int32_t H);
+int tavsr_fastattn_pool(const float* x, int64_t ldx, const float* cs, const float* W, const float* bias, const int64_t* lens,
+                        float* score_ws, float* w_out, float* pooled, int32_t B, int32_t T, int32_t D, int32_t H,
+                        tavsr_stream_t stream);
+int tavsr_fastattn_scale_rows(const float* q, int64_t ldq, const float* pk, float* wv, int32_t B, int32_t T, int32_t D,
+                              tavsr_stream_t stream);
+int tavsr_fastattn_bwd_pool(const float* dwv, int64_t lddwv, const float* q, int64_t ldq, const int64_t* lens, float* dpk,
+                            int32_t B, int32_t T, int32_t D, tavsr_stream_t stream);
+int64_t tavsr_fastattn_bwd_ws(int32_t B, int32_t T, int32_t D, int32_t H);
+int tavsr_fastattn_bwd_rows(int32_t is_k, const float* x, int64_t ldx, const float* cs, const float* w_pool, const float* dpool,
+                            const float* pool, const float* W, const int64_t* lens, const float* dres, int64_t lddres,
+                            const float* dwv, int64_t lddwv, const float* pk, float* dx, int64_t lddx, float* dWb,
+                            float* dcs, float* ws, int32_t B, int32_t T, int32_t D, int32_t H, tavsr_stream_t stream);
+/* Absolute positional encodings as an encoder embed (espnet PositionalEncoding / ScaledPositionalEncoding):
+ * y[b,t,:] = xscale * x[b,t,:] + a * pe[t,:] with a = alpha_dev[0] (a device scalar, the learnable `alpha`) or 1 (NULL);
+ * x, y contiguous [B][T][D], pe [T][D].  tavsr_add_pe_dalpha: dalpha[0] = sum dy * pe over 128 fixed block shares summed in
+ * order (ws >= tavsr_add_pe_dalpha_ws() floats): the same bits every run. */
+int tavsr_add_pe(const float* x, const float* pe, const float* alpha_dev, float xscale, float* y, int32_t B, int32_t T, int32_t D,
+                 tavsr_stream_t stream);
+int64_t tavsr_add_pe_dalpha_ws(void);
+int tavsr_add_pe_dalpha(const float* dy, const float* pe, float* dalpha, float* ws, int32_t B, int32_t T, int32_t D,
+                        tavsr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

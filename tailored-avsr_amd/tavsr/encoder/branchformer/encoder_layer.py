@@ -12,7 +12,7 @@ from typing import Optional
 import torch
 
 from ... import functional as F_
-from ...layers import LayerNorm
+from ...layers import FastSelfAttention, LayerNorm, RelPositionMultiHeadedAttention
 
 
 class MyBranchformerEncoderLayer(torch.nn.Module):
@@ -72,7 +72,13 @@ class MyBranchformerEncoderLayer(torch.nn.Module):
     # ---- gather parameters in the order BranchformerLayerFn expects (None for absent modules)
     def _params(self):
         from ..._lib import cached_params
-        return cached_params(self, F_.BF_PARAM_NAMES)
+        return cached_params(self, F_.FAST_PARAM_NAMES if isinstance(self.attn, FastSelfAttention) else F_.BF_PARAM_NAMES)
+
+    def _attn_kind(self) -> str:
+        """which of the three attention forms the layer dispatches on (encoder_layer.py:204-210)"""
+        if isinstance(self.attn, FastSelfAttention):
+            return "fast_selfattn"
+        return "rel_selfattn" if (self.attn is None or isinstance(self.attn, RelPositionMultiHeadedAttention)) else "selfattn"
 
     def _active_dropout(self) -> bool:
         rates = [self.dropout_rate]
@@ -81,21 +87,29 @@ class MyBranchformerEncoderLayer(torch.nn.Module):
         return self.training and any(r > 0 for r in rates)
 
     def forward(self, x_input, mask, cache=None, lens: Optional[torch.Tensor] = None):
-        """x_input: (x[B,T,size], pos_emb[1,2T-1,size]); mask: (B,1,T) bool prefix mask or None.
+        """x_input: (x[B,T,size], pos_emb[1,2T-1,size]) with the relative-position attention, the tensor x alone with ``selfattn``
+        / ``fast_selfattn`` (absolute positions are in x); the output has the input's form.  mask: (B,1,T) bool prefix mask or None.
 
         ``lens`` (int64 [B], valid frames) may be supplied by the encoder to avoid recomputing it from
         the mask; masks on this path are always length prefixes (encoder.py:345)."""
         if cache is not None:
             raise NotImplementedError("cache is not None, which is not tested")
-        if not isinstance(x_input, tuple):
+        kind = self._attn_kind()
+        if isinstance(x_input, tuple):
+            x, pos_emb = x_input
+        elif kind == "rel_selfattn" and self.attn is None:
             raise NotImplementedError("the HIP path implements the rel_pos form: x_input = (x, pos_emb)")
-        x, pos_emb = x_input
+        else:
+            x, pos_emb = x_input, None
+        if self.attn is not None and (pos_emb is None) == (kind == "rel_selfattn"):
+            raise ValueError(f"attention {kind} takes " + ("x_input = (x, pos_emb)" if kind == "rel_selfattn" else "the tensor x alone"))
+        back = (lambda y: (y, pos_emb)) if isinstance(x_input, tuple) else (lambda y: y)
         coeff = 1.0
         if self.training and self.stochastic_depth_rate > 0:
             skip = torch.rand(1).item() < self.stochastic_depth_rate
             coeff = 1.0 / (1 - self.stochastic_depth_rate)
             if skip:
-                return (x, pos_emb), mask
+                return back(x), mask
         merge = self.merge_method
         cgmlp_weight = self.cgmlp_weight
         dropped = False
@@ -108,7 +122,7 @@ class MyBranchformerEncoderLayer(torch.nn.Module):
         if lens is None and mask is not None:
             lens = mask.squeeze(1).sum(-1).to(torch.int64)
         cfg = dict(heads=self.attn.h if self.attn is not None else 1, ffn_act=self.feed_forward.activation,
-                   merge=merge, has_attn=self.attn is not None, has_mlp=self.cgmlp is not None,
+                   merge=merge, has_attn=self.attn is not None, has_mlp=self.cgmlp is not None, attn_kind=kind,
                    cgmlp_weight=cgmlp_weight, coeff=coeff,
                    merge_identity=isinstance(self.merge_proj, torch.nn.Identity),
                    # train-mode dropout (self.dropout / PositionwiseFeedForward / csgu: dropout_rate; attention
@@ -122,4 +136,4 @@ class MyBranchformerEncoderLayer(torch.nn.Module):
         elif w is not None:  # (B,2) -> the reference's (B,1,1) views (encoder_layer.py:286-289)
             self.weight_global = w[:, 0].view(-1, 1, 1)
             self.weight_local = w[:, 1].view(-1, 1, 1)
-        return (y, pos_emb), mask
+        return back(y), mask

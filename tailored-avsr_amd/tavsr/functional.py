@@ -48,8 +48,9 @@ def _note_ctx(ctx):
 # ------------------------------------------------------------------------------------------------
 # building blocks shared by the Functions: tavsr/layer_blocks.py (re-exported: tests and scripts reach them as F_._FFN, ...)
 # ------------------------------------------------------------------------------------------------
-from .layer_blocks import (EPS_ESPNET, FF_PARAMS, FFM_PARAMS, AttnBranch, AttnSaved, CgmlpBranch, CgmlpSaved, FFNSaved,  # noqa: E402,F401
-                           _AttnFused, _drop_, _drop_bwd, _drop_bwd_, _FFN, _SelfAttnCore)
+from .layer_blocks import (EPS_ESPNET, FAST_ATTN_PARAMS, FF_PARAMS, FFM_PARAMS, AttnBranch, AttnSaved, CgmlpBranch,  # noqa: E402,F401
+                           CgmlpSaved, FastAttnBranch, FastAttnSaved, FFNSaved, _AttnFused, _drop_, _drop_bwd, _drop_bwd_, _FFN,
+                           _SelfAttnCore)
 
 # the positional chain of the attention branch's backward with the layer's weight gradients, beside the chain (read here at call
 # time and passed down as ``lazy``: tests flip it on this module)
@@ -101,7 +102,15 @@ _I = {n: i for i, n in enumerate(BF_PARAM_NAMES)}
 EBF_PARAM_NAMES = BF_PARAM_NAMES + ("depthwise_conv_fusion.weight", "depthwise_conv_fusion.bias")
 
 
+# ... of a Branchformer layer whose attention is FastSelfAttention (``fast_selfattn``): its ten parameters in place of the
+# relative-position attention's eleven.  A list of its own for the same reason.
+_QI = BF_PARAM_NAMES.index("attn.linear_q.weight")
+FAST_PARAM_NAMES = BF_PARAM_NAMES[:_QI] + FAST_ATTN_PARAMS + tuple(n for n in BF_PARAM_NAMES[_QI:] if not n.startswith("attn."))
+
+
 def _param_names(cfg):
+    if cfg.get("attn_kind") == "fast_selfattn":
+        return FAST_PARAM_NAMES
     return EBF_PARAM_NAMES if cfg["merge"] == "dwconv" else BF_PARAM_NAMES
 
 
@@ -110,6 +119,8 @@ def _layer_c_ok(x, cfg, P, pd, pos_emb=None) -> bool:
     library's to judge (tavsr_branchformer_layer_ok).  Un-captured loops only unless TAVSR_LAYER_C=capture: a captured step
     replays the same kernels either way, and the capture of the Python sequencing measured 1 % faster (allocation order)."""
     if not ops.LAYER_C or ops.PROFILE is not None or (ops.LAYER_C_EAGER_ONLY and torch.cuda.is_current_stream_capturing()):
+        return False
+    if cfg.get("attn_kind", "rel_selfattn") != "rel_selfattn" or pos_emb is None:      # the sequencer knows the rel_pos attention alone
         return False
     if not (cfg["has_attn"] and cfg["has_mlp"] and cfg["merge"] == "learned_ave" and not cfg["merge_identity"]):
         return False
@@ -492,7 +503,15 @@ class BranchformerLayerFn(torch.autograd.Function):
         xa = xm = rd_a = rd_m = None
         br = ops.BranchScope(two)     # attention branch beside the cgMLP branch (joined before the merge)
         with br:
-            if has_attn:
+            if has_attn and cfg.get("attn_kind") == "fast_selfattn":
+                # x1 = dropout(attn(x1, mask)): the module's output is the branch's (no linear_out); FastSelfAttention's three
+                # dropouts run at attention_dropout_rate (encoder.py:250-257), the layer's own at dropout_rate
+                xa, s = FastAttnBranch.fwd(nbr[0], p, lens, B, T, cfg["heads"], cfg.get("p_att", 0.0), out=cat)
+                t_xa = None
+                if cat is None and pd > 0.0:
+                    xa, t_xa = ops.dropout(xa, pd)
+                sv["attn"] = s._replace(mean=bmean, rstd=brstd, t_br=t_xa)
+            elif has_attn:
                 cx, s = AttnBranch.fwd(nbr[0], p, pos_emb, lens, B, T, cfg["heads"], cfg.get("p_att", 0.0))
                 xa, t_xa, rd_a = _bf_branch_out(cx, p["attn.linear_out.weight"], p["attn.linear_out.bias"], cat, 0, pd,
                                                 (mp[0], mp[4]) if use_rd else None)
@@ -557,8 +576,11 @@ class BranchformerLayerFn(torch.autograd.Function):
                 sa = sv["attn"]
                 if sa.t_br is not None and not masked:
                     dxa = _drop_bwd(dxa.contiguous(), sa.t_br)
-                dn_a, late = AttnBranch.bwd(dxa, sa, p, ctx.pos_emb, ctx.lens, B, T, cfg["heads"], grp, G,
-                                            lazy=beside and _POS_DW_BESIDE)
+                if cfg.get("attn_kind") == "fast_selfattn":
+                    dn_a = FastAttnBranch.bwd(dxa, sa, p, ctx.lens, B, T, cfg["heads"], grp, G)
+                else:
+                    dn_a, late = AttnBranch.bwd(dxa, sa, p, ctx.pos_emb, ctx.lens, B, T, cfg["heads"], grp, G,
+                                                lazy=beside and _POS_DW_BESIDE)
         if has_mlp:
             sm = sv["mlp"]
             if sm.t_br is not None and not masked:
@@ -650,6 +672,26 @@ class InterCTCConditionFn(torch.autograd.Function):
         dh = ops.empty(M, D, like=dy2)
         ops.gemm(M, D, V, dl2, S, ctc_w, ctc_w.stride(0), dh, D, b_kmajor=True)
         return dy, dh.view(shp), gw, gb, gcw, gcb
+
+
+class AddPEFn(torch.autograd.Function):
+    """xscale * x + alpha * pe[:T]: the absolute positional encodings as an encoder embed (espnet PositionalEncoding: xscale =
+    sqrt(d), no alpha; ScaledPositionalEncoding: xscale = 1, ``alpha`` the learnable scalar, read on the device)."""
+
+    @staticmethod
+    def forward(ctx, x, alpha, pe, xscale):
+        ctx.pe, ctx.xscale, ctx.has_alpha = pe, xscale, alpha is not None
+        return ops.add_pe(x, pe, alpha, xscale)
+
+    @staticmethod
+    @guarded
+    def backward(ctx, dy):
+        dy = dy.contiguous()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = dy if ctx.xscale == 1.0 else ops.axpby(dy, None, ctx.xscale, 0.0)
+        da = ops.add_pe_dalpha(dy, ctx.pe).view(()) if ctx.has_alpha and ctx.needs_input_grad[1] else None
+        return dx, da, None, None
 
 
 class DropoutFn(torch.autograd.Function):

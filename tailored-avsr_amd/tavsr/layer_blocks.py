@@ -59,6 +59,21 @@ class AttnSaved(NamedTuple):
     t_br: Any
 
 
+class FastAttnSaved(NamedTuple):
+    """kept by the additive-attention branch: statistics of the branch's LayerNorm and its output ``n``, the q | k rows, the core's
+    state (ops.fastattn_fwd: the two pooling weights [B, H, T], the pooled vectors before and after their dropout, their tokens),
+    the rows ``wv`` = pk * q that ``transform`` reads, and the tokens of the module's output dropout and of the layer's.  ``mean``,
+    ``rstd`` and ``t_br`` are filled in by the caller of ``FastAttnBranch.fwd``."""
+    mean: Any
+    rstd: Any
+    n: Any
+    qk: Any
+    core: Any
+    wv: Any
+    t_tr: Any
+    t_br: Any
+
+
 class CgmlpSaved(NamedTuple):
     """kept by the cgMLP branch: statistics of the branch's LayerNorm and its output ``n``, channel_proj1's output ``g`` = gelu(z),
     the CSGU's normalised gate half with its statistics, the gated rows ``u``, the depthwise convolution's output and the tokens
@@ -283,11 +298,20 @@ class AttnBranch:
 
     @staticmethod
     def fwd(n, p, pos_emb, lens, B, T, H, p_att):
-        """normalised rows ``n`` [B*T, D] -> (context rows cx, AttnSaved without mean / rstd / t_br)"""
+        """normalised rows ``n`` [B*T, D] -> (context rows cx, AttnSaved without mean / rstd / t_br).  ``pos_emb`` None: plain
+        multi-head attention over absolute positions (espnet MultiHeadedAttention, ``selfattn``): no positional rows, no head
+        biases; ``pp``, ``qu`` and ``qv`` stay ``None`` and ``attn`` tells the core (a tuple: the fused one)."""
         M, D = n.shape
         dk = D // H
         qkv = ops.empty(M, 3 * D, like=n)
         ops.linear_group(n, [(p[f"attn.linear_{c}.weight"], p[f"attn.linear_{c}.bias"], j * D) for j, c in enumerate("qkv")], qkv)
+        if pos_emb is None:
+            if ops.ATTN_FUSED and dk == 64:
+                t_att = None
+                cx, attn = _AttnFused.fwd(qkv, 0, qkv, D, qkv, 2 * D, B, T, T, H, dk, lens, False, p_att=p_att)
+            else:
+                cx, attn, t_att = _SelfAttnCore.fwd(qkv, 3 * D, 0, qkv, 3 * D, D, qkv, 3 * D, 2 * D, B, T, T, H, dk, lens, False, p_att=p_att)
+            return cx, AttnSaved(mean=None, rstd=None, n=n, qkv=qkv, pp=None, qu=None, qv=None, cx=cx, attn=attn, t_att=t_att, t_br=None)
         pp = ops.linear(pos_emb.reshape(-1, D), p["attn.linear_pos.weight"])
         bias_u, bias_v = p["attn.pos_bias_u"].reshape(-1), p["attn.pos_bias_v"].reshape(-1)
         if ops.ATTN_FUSED and dk == 64:
@@ -313,6 +337,15 @@ class AttnBranch:
         G["attn.linear_out.weight"], G["attn.linear_out.bias"] = grp.add(d_out, s.cx, alpha=alpha, bias_grad=True)
         dcx = ops.linear_dx(d_out, p["attn.linear_out.weight"], alpha=alpha)
         dqkv = torch.empty_like(s.qkv)
+        if pos_emb is None:      # plain multi-head attention: dQ goes straight into its window
+            if isinstance(s.attn, tuple):
+                _AttnFused.bwd(dcx, s.cx, s.attn, s.qkv, 0, s.qkv, D, s.qkv, 2 * D, dqkv, 0, dqkv, D, dqkv, 2 * D, B, T, T, H, dk, lens, False)
+            else:
+                _SelfAttnCore.bwd(dcx, s.attn, s.qkv, 3 * D, 0, s.qkv, 3 * D, D, s.qkv, 3 * D, 2 * D, dqkv, 3 * D, 0, dqkv, 3 * D, D,
+                                  dqkv, 3 * D, 2 * D, B, T, T, H, dk, tok=s.t_att)
+            for j, c in enumerate("qkv"):
+                G[f"attn.linear_{c}.weight"], G[f"attn.linear_{c}.bias"] = grp.add(dqkv[:, j * D:(j + 1) * D], s.n, bias_grad=True)
+            return ops.linear_dx_cat(dqkv, [p[f"attn.linear_{c}.weight"] for c in "qkv"]), []
         dqu = ops.empty(M, D, like=d_out)
         if s.qu is None:         # fused attention core
             dqv, dp = _AttnFused.bwd(dcx, s.cx, s.attn, s.qkv, 0, s.qkv, D, s.qkv, 2 * D, dqu, 0, dqkv, D, dqkv, 2 * D, B, T, T, H, dk,
@@ -332,6 +365,57 @@ class AttnBranch:
             G[f"attn.linear_{c}.weight"], G[f"attn.linear_{c}.bias"] = grp.add(dqkv[:, j * D:(j + 1) * D], s.n, bias_grad=True)
         dn = ops.linear_dx_cat(dqkv, [p[f"attn.linear_{c}.weight"] for c in "qkv"])      # one K = 3D GEMM
         return dn, late
+
+
+# the ten parameters of FastSelfAttention
+FAST_ATTN_PARAMS = tuple(f"attn.{m}.{w}" for m in ("query", "query_att", "key", "key_att", "transform") for w in ("weight", "bias"))
+
+
+class FastAttnBranch:
+    """The additive-attention branch of an encoder layer behind its LayerNorm (espnet2 FastSelfAttention, ``fast_selfattn``;
+    src/encoder/branchformer/encoder_layer.py:204-210: ``self.attn(x1, mask)``, no output projection of the layer's):
+    q | k = query(n) | key(n), the pooling core on csrc/fastattn.hip, out = dropout(transform(pk * q)) + q.  The LayerNorm in front
+    and the layer's dropout on ``out`` are the caller's."""
+
+    @staticmethod
+    def fwd(n, p, lens, B, T, H, p_drop, out=None):
+        """normalised rows ``n`` [B*T, D] -> (the module's output rows, FastAttnSaved without mean / rstd / t_br).  ``out``: a
+        [M, >= D] buffer whose first D columns receive the output (the concat merge's window); without dropout the transform GEMM
+        writes there itself, with it the masked result is copied in (one more pass over [M, D])."""
+        M, D = n.shape
+        qk = ops.empty(M, 2 * D, like=n)
+        ops.linear_group(n, [(p["attn.query.weight"], p["attn.query.bias"], 0), (p["attn.key.weight"], p["attn.key.bias"], D)], qk)
+        wv, core = ops.fastattn_fwd(qk, p["attn.query_att.weight"], p["attn.query_att.bias"], p["attn.key_att.weight"],
+                                    p["attn.key_att.bias"], lens, B, T, D, H, p=p_drop)
+        if out is not None and not (p_drop and p_drop > 0.0):
+            ops.linear(wv, p["attn.transform.weight"], p["attn.transform.bias"], res=qk[:, :D], out=out, out_off=0, ldc=out.shape[1])
+            out, t_tr = out[:, :D], None
+        else:
+            y, t_tr = ops.linear_drop(wv, p["attn.transform.weight"], p["attn.transform.bias"], p_drop, res=qk[:, :D])
+            if out is not None:
+                ops.axpby2d(y, None, 1.0, 0.0, out[:, :D])
+                y = out[:, :D]
+            out = y
+        return out, FastAttnSaved(mean=None, rstd=None, n=n, qk=qk, core=core, wv=wv, t_tr=t_tr, t_br=None)
+
+    @staticmethod
+    def bwd(d_out, saved, p, lens, B, T, H, grp, G):
+        """``d_out``: gradient of the module's output (under the layer's dropout mask).  Returns the gradient of the normalised
+        rows; fills ``G`` (the three projections' weight gradients through ``grp``; the four score gradients come from the
+        core's fixed-order partial sums)."""
+        s = saved
+        M, D = s.wv.shape
+        if s.t_tr is not None and not d_out.is_contiguous():      # (the concat merge hands over a column window)
+            d_out = d_out.contiguous()
+        dyt = _drop_bwd(d_out, s.t_tr)
+        G["attn.transform.weight"], G["attn.transform.bias"] = grp.add(dyt, s.wv, bias_grad=True)
+        dwv = ops.linear_dx(dyt, p["attn.transform.weight"])
+        dqk, gwq, gbq, gwk, gbk = ops.fastattn_bwd(dwv, d_out, s.qk, s.core, p["attn.query_att.weight"], p["attn.key_att.weight"],
+                                                   lens, B, T, D, H)
+        G["attn.query_att.weight"], G["attn.query_att.bias"], G["attn.key_att.weight"], G["attn.key_att.bias"] = gwq, gbq, gwk, gbk
+        G["attn.query.weight"], G["attn.query.bias"] = grp.add(dqk[:, :D], s.n, bias_grad=True)
+        G["attn.key.weight"], G["attn.key.bias"] = grp.add(dqk[:, D:], s.n, bias_grad=True)
+        return ops.linear_dx_cat(dqk, [p["attn.query.weight"], p["attn.key.weight"]])
 
 
 class CgmlpBranch:

@@ -71,6 +71,36 @@ class MultiHeadedAttention(nn.Module):
         self.dropout_rate = dropout_rate
 
 
+class FastSelfAttention(nn.Module):
+    """espnet2 asr/layers/fastformer.py: Fastformer's additive attention, linear in the sequence length (the ``fast_selfattn``
+    option of the Branchformer encoder).  ``query`` / ``key`` / ``transform`` project size -> size (the value is the query:
+    shared parameters), ``query_att`` / ``key_att`` give one score per head from ALL ``size`` columns.  The arithmetic is
+    ``layer_blocks.FastAttnBranch`` on csrc/fastattn.hip, whose range (``ops.FASTATTN_LIMIT``) is checked here."""
+
+    def __init__(self, size, attention_heads, dropout_rate):
+        super().__init__()
+        if size % attention_heads != 0:
+            raise ValueError(f"Hidden size ({size}) is not an integer multiple of attention heads ({attention_heads})")
+        if not ops.fastattn_ok(size, attention_heads):
+            raise ValueError(f"FastSelfAttention on the HIP path takes {ops.FASTATTN_LIMIT}: got size {size}, "
+                             f"attention_heads {attention_heads}")
+        self.attention_head_size = size // attention_heads
+        self.num_attention_heads = self.h = attention_heads
+        self.query = nn.Linear(size, size)
+        self.query_att = nn.Linear(size, attention_heads)
+        self.key = nn.Linear(size, size)
+        self.key_att = nn.Linear(size, attention_heads)
+        self.transform = nn.Linear(size, size)
+        self.dropout_rate = dropout_rate
+
+    def espnet_initialization_fn(self):
+        for m in self.modules():
+            if isinstance(m, nn.Linear):
+                m.weight.data.normal_(mean=0.0, std=0.02)
+                if m.bias is not None:
+                    m.bias.data.zero_()
+
+
 class RelPositionMultiHeadedAttention(MultiHeadedAttention):
     def __init__(self, n_head, n_feat, dropout_rate, zero_triu=False):
         super().__init__(n_head, n_feat, dropout_rate)
@@ -139,7 +169,8 @@ class RelPositionalEncoding(nn.Module):
 
 
 class PositionalEncoding(nn.Module):
-    """Absolute sinusoid table of the decoder embed; applied inside tavsr_embed_pe."""
+    """Absolute sinusoid table.  The decoder embed applies it inside tavsr_embed_pe; as an encoder embed (``abs_pos``)
+    ``forward(x)`` = dropout(x * sqrt(d) + pe[:T]) - ``prescaled``: the producer GEMM has already multiplied by sqrt(d)."""
 
     def __init__(self, d_model, dropout_rate, max_len=5000):
         super().__init__()
@@ -157,6 +188,21 @@ class PositionalEncoding(nn.Module):
             self._cache[key] = self._pe_host[:L].contiguous().to(device)
         return self._cache[key]
 
+    def forward(self, x, prescaled=False):
+        y = F_.AddPEFn.apply(x.contiguous(), self._parameters.get("alpha"), self.table(x.size(1), x.device), 1.0 if prescaled else self.xscale)
+        if self.training and self.dropout_rate > 0:
+            y = F_.DropoutFn.apply(y, self.dropout_rate)
+        return y
+
+
+class ScaledPositionalEncoding(PositionalEncoding):
+    """espnet ScaledPositionalEncoding (``scaled_abs_pos``): dropout(x + alpha * pe[:T]) with one learnable scalar, no sqrt(d)."""
+
+    def __init__(self, d_model, dropout_rate, max_len=5000):
+        super().__init__(d_model, dropout_rate, max_len)
+        self.xscale = 1.0
+        self.alpha = nn.Parameter(torch.tensor(1.0))
+
 
 class TooShortUttError(Exception):
     def __init__(self, message, actual_size, limit):
@@ -171,13 +217,16 @@ class Conv2dSubsampling(nn.Module):
         super().__init__()
         self.conv = nn.Sequential(nn.Conv2d(1, odim, 3, 2), nn.ReLU(), nn.Conv2d(odim, odim, 3, 2), nn.ReLU())
         if pos_enc is None:
-            raise ValueError("the HIP path is built with a RelPositionalEncoding (rel_pos configs)")
+            raise ValueError("the HIP path is built with the encoder's positional encoding (rel_pos, abs_pos or scaled_abs_pos configs)")
         self.out = nn.Sequential(nn.Linear(odim * (((idim - 1) // 2 - 1) // 2), odim), pos_enc)
 
     def forward(self, x, x_mask):
-        pe: RelPositionalEncoding = self.out[1]
+        pe = self.out[1]
         y = F_.Conv2dSubsamplingFn.apply(x, self.conv[0].weight, self.conv[0].bias, self.conv[2].weight,
                                          self.conv[2].bias, self.out[0].weight, self.out[0].bias, pe.xscale)
+        if isinstance(pe, PositionalEncoding):      # absolute encodings: a tensor, not (x, pos_emb); sqrt(d) rode in the GEMM
+            y = pe(y, prescaled=True)
+            return y, (None if x_mask is None else x_mask[:, :, :-2:2][:, :, :-2:2])
         pos = pe.pos_emb(y.size(1), y.device)
         if self.training and pe.dropout_rate > 0:    # RelPositionalEncoding: dropout(x), dropout(pos_emb)
             y = F_.DropoutFn.apply(y, pe.dropout_rate)

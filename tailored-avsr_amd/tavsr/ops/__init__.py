@@ -29,6 +29,10 @@ LN_BWD_DROP = True      # masked gradient copy from the LayerNorm backward (test
 # launch per direction.  TAVSR_ATTN_FUSED=0 keeps the GEMM + softmax chain (A/B switch; also the path for head sizes != 64).
 ATTN_FUSED = True
 
+# Additive attention (csrc/fastattn.hip): what tavsr_fastattn_ok takes; FastSelfAttention's constructor refuses the rest in these words
+# (the range itself: ops.fastattn_ok in ops/fastattn.py and fa_shape_ok in csrc/fastattn.hip - the three change together)
+FASTATTN_LIMIT = "1 <= attention_heads <= 8, size <= 512, size / attention_heads a multiple of 4"
+
 # ---------------------------------------------------------------------------------------------- blocks
 # Streaming feed-forward block (csrc/ffn2.hip, round 3): LayerNorm prologue + both GEMMs in one launch whose weights stream
 # through per-wave LDS-DMA rings, + a finishing launch that can also emit the LayerNorms the consumers of y start with.
@@ -120,6 +124,7 @@ from .blocks import *  # noqa: E402,F401,F403
 from .matmul import *  # noqa: E402,F401,F403
 from .norm import *  # noqa: E402,F401,F403
 from .attention import *  # noqa: E402,F401,F403
+from .fastattn import *  # noqa: E402,F401,F403
 from .vision import *  # noqa: E402,F401,F403
 from .losses import *  # noqa: E402,F401,F403
 from .search import *  # noqa: E402,F401,F403
