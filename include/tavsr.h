@@ -213,6 +213,8 @@ int tavsr_gemm_tune(const tavsr_gemm_desc* desc, int32_t cfg, int32_t nsplit, ta
  * D <= 1024, rows 16-byte aligned.  mean/rstd [M] are saved for backward (may be NULL in fwd).
  * bwd: dx = dx_add + LN'(dy) (dx_add may be NULL; lets the caller fold a residual-branch gradient
  * in), dgamma/dbeta are overwritten or accumulated; ws >= tavsr_layernorm_bwd_ws(M, D) floats.
+ * M == 0 (tavsr_layernorm_bwd, _bwd_act): the empty sum - dgamma = dbeta = 0, or left as they were under `accumulate`; dx and ws are
+ * not touched (tavsr_layernorm_bwd_ws(0, D) == 0).
  * ------------------------------------------------------------------------------------------- */
 int tavsr_layernorm_fwd(const float* x, int64_t ldx, const float* gamma, const float* beta, float eps,
                         float* y, int64_t ldy, float* mean, float* rstd, int32_t M, int32_t D,
@@ -224,7 +226,8 @@ int tavsr_layernorm_bwd(const float* dy, int64_t lddy, const float* x, int64_t l
                         float* ws, int32_t M, int32_t D, tavsr_stream_t stream);
 
 /* Column sums out[n] (+)= scale * sum_m x[m*ldx + n]: bias gradients of every Linear, pos_bias_u/v
- * gradients.  ws >= tavsr_colsum_ws(M, N) floats.  Deterministic (two-stage, no atomics). */
+ * gradients.  ws >= tavsr_colsum_ws(M, N) floats.  Deterministic (two-stage, no atomics).  M == 0: out = scale * 0, or out
+ * as it was under `accumulate`; tavsr_colsum_ws(0, N) == 0 and ws (like x, which may be NULL then) is not touched. */
 /* main pass only: dx and per-block partials (dgamma | dbeta) at ws[blk*ws_ld + 0..2D), blk < tavsr_layernorm_bwd_ws(M,D)/(2D);
  * several LayerNorms of one backward node write into one slab and share one tavsr_sum_partials launch */
 int tavsr_layernorm_bwd_partial(const float* dy, int64_t lddy, const float* x, int64_t ldx, const float* mean,
@@ -270,6 +273,7 @@ int tavsr_sum_partials2(const float* part, int32_t nparts, int64_t stride, float
  *                  rel_shift(bd)[i,j] = bd[i, T-1-i+j]
  *   softmax_bwd  : ds = attn*(dattn - <attn,dattn>)*scale and (optional) its un-shifted copy
  *                  ds_skew[i, T-1-i+j] = ds[i,j], 0 elsewhere, that feeds the positional GEMMs
+ * Padding columns: attn and ds leave columns T2.. of a row, ds_skew columns W.., untouched; the padding of the inputs is never read.
  * ------------------------------------------------------------------------------------------- */
 int tavsr_add_head_bias(const float* q, int64_t ldq, const float* u, const float* v, float* qu, float* qv,
                         int64_t M, int32_t D, tavsr_stream_t stream);
@@ -281,7 +285,8 @@ int tavsr_softmax_bwd(const float* attn, const float* dattn, float* ds, float* d
                       tavsr_stream_t stream);
 /* tavsr_softmax_fwd / _bwd with the dropout of the attention probabilities (espnet forward_attention: self.dropout(attn))
  * folded in: pv = dropout(attn, p) with exactly the mask tavsr_dropout(attn, ..., offset) draws (rows padded to ld_s % 4 == 0);
- * the backward takes the gradient w.r.t. pv and regenerates the mask. */
+ * the backward takes the gradient w.r.t. pv and regenerates the mask.  pv's padding columns T2.. are written as 0 (attn's, ds's and
+ * ds_skew's stay untouched, as above). */
 int tavsr_softmax_dropout_fwd(const float* ac, const float* bd, const int64_t* klens, float* attn, float* pv, int32_t H, int32_t B,
                               int32_t T1, int32_t T2, int32_t W, int64_t ld_s, int64_t ld_w, float scale, int32_t causal, float p,
                               const uint64_t* seed_dev, uint64_t offset, tavsr_stream_t stream);

@@ -405,8 +405,9 @@ extern "C" int tavsr_layernorm_bwd(const float* dy, int64_t lddy, const float* x
   TAVSR_REQUIRE(dgamma && dbeta, TAVSR_EINVAL, "layernorm_bwd: null pointer");
   int rc = tavsr_layernorm_bwd_partial(dy, lddy, x, ldx, mean, rstd, gamma, dx_add, ldadd, dx, lddx, ws, 2 * (int64_t)D, M, D,
                                        stream);
-  if (rc || M <= 0) return rc;
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(cdiv(2 * D, 64)), dim3(kSumWaves * 64), 0, (hipStream_t)stream, ws, ln_blocks(M),
+  if (rc || (M <= 0 && accumulate)) return rc;
+  // M == 0: no partial row was written and none is read - the empty sum, dgamma = dbeta = 0
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(cdiv(2 * D, 64)), dim3(kSumWaves * 64), 0, (hipStream_t)stream, ws, M > 0 ? ln_blocks(M) : 0,
                      (int64_t)2 * D, dgamma, dbeta, D, 2 * D, accumulate, 1.f);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
@@ -421,8 +422,9 @@ extern "C" int tavsr_layernorm_bwd_act(const float* dy, int64_t lddy, const floa
   TAVSR_REQUIRE(dgamma && dbeta && z, TAVSR_EINVAL, "layernorm_bwd_act: null pointer");
   int rc = layernorm_bwd_partial_impl(dy, lddy, x, ldx, mean, rstd, gamma, nullptr, 0, dx, lddx, ws, 2 * (int64_t)D, M, D, z, ldz, act,
                                       stream);
-  if (rc || M <= 0) return rc;
-  hipLaunchKernelGGL(sum_partials_kernel, dim3(cdiv(2 * D, 64)), dim3(kSumWaves * 64), 0, (hipStream_t)stream, ws, ln_blocks(M),
+  if (rc || (M <= 0 && accumulate)) return rc;
+  // M == 0: no partial row was written and none is read - the empty sum, dgamma = dbeta = 0
+  hipLaunchKernelGGL(sum_partials_kernel, dim3(cdiv(2 * D, 64)), dim3(kSumWaves * 64), 0, (hipStream_t)stream, ws, M > 0 ? ln_blocks(M) : 0,
                      (int64_t)2 * D, dgamma, dbeta, D, 2 * D, accumulate, 1.f);
   TAVSR_LAUNCH_CHECK();
   return TAVSR_OK;
@@ -432,13 +434,15 @@ extern "C" int64_t tavsr_colsum_ws(int32_t M, int32_t N) { return (int64_t)colsu
 
 extern "C" int tavsr_colsum(const float* x, int64_t ldx, int32_t M, int32_t N, float scale, float* out,
                             int32_t accumulate, float* ws, tavsr_stream_t stream) {
-  TAVSR_REQUIRE(x && out && ws, TAVSR_EINVAL, "colsum: null pointer");
+  TAVSR_REQUIRE((x || M <= 0) && out && (ws || M <= 0), TAVSR_EINVAL, "colsum: null pointer");
   if (N <= 0) return TAVSR_OK;
   hipStream_t s = (hipStream_t)stream;
-  const int chunks = M > 0 ? colsum_chunks(M) : 1;
-  const int rpc = M > 0 ? cdiv(M, chunks) : 1;
-  hipLaunchKernelGGL(colsum_part_kernel, dim3(cdiv(N, 64), chunks), dim3(256), 0, s, x, ldx, M, N, rpc, ws);
-  TAVSR_LAUNCH_CHECK();
+  // M == 0: tavsr_colsum_ws(0, N) is 0 floats, so nothing may be parked in ws - the reduction runs over no partial row (the empty sum)
+  const int chunks = M > 0 ? colsum_chunks(M) : 0;
+  if (chunks > 0) {
+    hipLaunchKernelGGL(colsum_part_kernel, dim3(cdiv(N, 64), chunks), dim3(256), 0, s, x, ldx, M, N, cdiv(M, chunks), ws);
+    TAVSR_LAUNCH_CHECK();
+  }
   hipLaunchKernelGGL(sum_partials_kernel, dim3(cdiv(N, 64)), dim3(kSumWaves * 64), 0, s, ws, chunks, (int64_t)N, out, out, N, N,
                      accumulate, scale);
   TAVSR_LAUNCH_CHECK();
