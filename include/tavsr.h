@@ -482,12 +482,13 @@ int tavsr_scale_dev(const float* x, const float* s, float c, float* out, int64_t
  * per utterance; gn = LayerNorm(gate half) is a tavsr_layernorm_fwd call on the strided half.
  *   gn, out, conv: [B*T, C];  r: gate-free half, row stride ldr;  w: [C, K] (torch [C,1,K]).
  * bwd: dr (row stride lddr), dgn, dw, dbias (overwritten, or added to with accumulate = 1);
- * ws >= tavsr_dwconv_gate_bwd_ws floats.
+ * ws >= tavsr_dwconv_gate_bwd_ws(B, T, C, K) floats: the size depends on T and K.
  * K: every odd kernel size from 1 to 63, any C and T (K may be wider than the utterance); an even K, K < 1
- * or K > 63: TAVSR_EUNSUPPORTED, nothing is launched.  K = 31 runs kernels of its own; every other K the
- * generic pair, whose dynamic LDS grows with K - forward (127 + 2K) * 256 bytes, backward (126 + 3K) * 256
- * bytes: 64,768 and 80,640 at K = 63 - and is opted in for (hipFuncAttributeMaxDynamicSharedMemorySize);
- * where the runtime does not grant that, the call returns TAVSR_EUNSUPPORTED and launches nothing.
+ * or K > 63: TAVSR_EUNSUPPORTED, nothing is launched.  K = 31 runs kernels of its own (csrc/cgmlp.hip); every
+ * other K the gate form of the depthwise-convolution tile core (csrc/dwconv_time.hip: static LDS, one partial
+ * slab per utterance and 256 time steps).  At K != 31 a shape beyond the core's index limits - B > 65535,
+ * B * T >= 2^31 or C * (K + 1) >= 2^31 - is refused with TAVSR_EUNSUPPORTED before anything is launched.
+ * B, T or C <= 0: TAVSR_OK, nothing is launched.
  * ------------------------------------------------------------------------------------------- */
 int tavsr_dwconv_gate_fwd(const float* gn, const float* r, int64_t ldr, const float* w, const float* bias,
                           float* out, float* conv, int32_t B, int32_t T, int32_t C, int32_t K,

@@ -212,7 +212,17 @@ int probe_fork(hipStream_t forked, hipStream_t caller, bool at_join);   // probe
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // dwconv_time.hip: the summed partial slab [C][K+1] of a depthwise convolution's backward -> dw [C][K] and dbias [C] (tap K is the
-// bias); shared by tavsr_dwconv_gate_bwd (cgmlp.hip), tavsr_dwconv_add_bwd and tavsr_glu_dwconv_bwd
+// bias); shared by the core's three forms and by tavsr_dwconv_gate_bwd's K = 31 kernel (cgmlp.hip)
 int dwconv_split(const float* sum, float* dw, float* dbias, int C, int K, int accumulate, hipStream_t stream);
+
+// dwconv_time.hip: its gate form, out = r * (bias + dwconv_K(gn)), behind tavsr_dwconv_gate_fwd / _bwd (cgmlp.hip) at K != 31.  Odd
+// K <= 63; an empty shape (B, T or C <= 0) launches nothing; a kernel size or a shape the core does not index: TAVSR_EUNSUPPORTED.
+// dt_bwd_ws: floats of workspace of the core's backward, any form
+int dt_gate_fwd(const float* gn, const float* r, int64_t ldr, const float* w, const float* bias, float* out, float* conv, int B, int T,
+                int C, int K, tavsr_stream_t stream);
+int dt_gate_bwd(const float* du, const float* gn, const float* r, int64_t ldr, const float* conv, const float* w, float* dr,
+                int64_t lddr, float* dgn, float* dw, float* dbias, int accumulate, float* ws, int B, int T, int C, int K,
+                tavsr_stream_t stream);
+int64_t dt_bwd_ws(int32_t B, int32_t T, int32_t C, int32_t K);
 
 }  // namespace tavsr

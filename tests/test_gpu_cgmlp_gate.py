@@ -1,6 +1,7 @@
-"""GPU: the cgMLP gate kernels of csrc/cgmlp.hip - the generic forward / backward pair at every kernel size class, the pair fixed at
-K = 31, the partial-slab reduction behind them, the ``accumulate`` and ``zr`` routes, the refusals, and CgmlpBranch on its unfused
-route - against tests/cgmlp_gate_ref.py in float64.
+"""GPU: the cgMLP gate behind tavsr_dwconv_gate_fwd / _bwd - the gate form of the depthwise-convolution tile core
+(csrc/dwconv_time.hip) at every kernel size class, the pair of csrc/cgmlp.hip fixed at K = 31, the partial-slab reduction behind
+them, the ``accumulate`` and ``zr`` routes, the refusals, and CgmlpBranch on its unfused route - against tests/cgmlp_gate_ref.py in
+float64.
 
 Tolerance (the convention of tests/test_gpu_ebf.py / test_gpu_conformer.py): the same chain is evaluated by the reference in fp32
 on the CPU; its error against float64 (e32) is what fp32 costs this computation, and the GPU may be four times as far from float64,
@@ -8,10 +9,11 @@ never asked for less than the project's kernel floors: 1e-5 on values (out, conv
 are compared as max |a - b| / max |b|, gradients as relative L2.  Every case prints both errors and their ratio before it asserts.
 Weights are scaled by K ** -0.5, so the convolution's output keeps the scale of its input at every K.
 
-The sweep: K on both sides of 31 and of the generic kernels' 48 KB / 64 KB dynamic-LDS requests (forward (127 + 2K) * 256 bytes,
-backward (126 + 3K) * 256: K = 43 65,280, K = 45 66,816, K = 63 80,640), K = 1 (no halo; waves 2 and 3 of the backward own no tap),
-K = 63 (all CG_TAPS accumulators); C = 64 (a whole tile), 67 (a 3-lane tail), 200 (three tiles and 8 lanes); T around the backward
-tile (64) and the forward tile (128), each with its halo, and T <= pad, where the window is wider than the utterance.
+The sweep: K on both sides of 31, K = 1 (no halo; waves 1 to 3 of the backward own no tap), K = 43 / 45 (sizes like any other: the gate uses
+no dynamic LDS), K = 63 (all 16 tap accumulators of the gate form, its 32-step tile filling the 96 LDS rows); C = 64 (a whole tile), 67 (a 3-lane tail), 200 (three tiles and 8 lanes); T around
+the gate form's tile (32), the K = 31 kernels' backward tile (64) and forward tile (128), each with its halo, around the gate form's
+backward chunk (256: at 257 an utterance gets a second partial slab of one step), and T <= pad, where the window is wider than the
+utterance.
 
 The measured gpu error / e32 ratios are recorded in profiles/cgmlp_gate_edges.txt.
 """
@@ -33,7 +35,8 @@ IS_VALUE = (True, True, False, False, False, False)
 
 def sweep_T(K):
     pad = (K - 1) // 2
-    return sorted({t for t in (1, 2, pad, pad + 1, 63, 64, 65, 64 + pad, 127, 128, 129, 128 + pad + 1, 200) if t > 0})
+    return sorted({t for t in (1, 2, pad, pad + 1, 31, 32, 33, 32 + pad + 1, 63, 64, 65, 64 + pad, 127, 128, 129, 128 + pad + 1, 200,
+                               255, 256, 257) if t > 0})
 
 
 def _bounded(name, gpu, f32, f64, floor, value=False):
@@ -175,12 +178,16 @@ def test_backward_accumulates_into_dw_and_dbias(K):
     assert torch.equal(dw1, pw + dw0) and torch.equal(db1, pb + db0)
 
 
-@pytest.mark.parametrize("B", [1, 17, 65])
+SLAB_T = {1: 2, 17: 2, 65: 2, 9: 257}
+
+
+@pytest.mark.parametrize("B", SLAB_T)
 def test_partial_slab_reduction_block_counts(B):
-    """one partial slab per utterance, summed by sum_partials_kernel, whose 16 waves take the slabs 16 apart, four at a time from
-    49 slabs on: B = 1 (15 idle waves), 17 (wave 0 takes two, the tail loop), 65 (wave 0 runs the unrolled loop once, then the
-    tail loop).  dw / dbias against float64, bit-equal across two runs"""
-    T, C, K = 2, 64, 3
+    """one partial slab per utterance and 256-step chunk, summed by sum_partials_kernel, whose 16 waves take the slabs 16 apart, four
+    at a time from 49 slabs on: T = 2 with B = 1 (15 idle waves), 17 (wave 0 takes two, the tail loop), 65 (wave 0 runs the unrolled
+    loop once, then the tail loop); B = 9 at T = 257, two chunks per utterance: 18 slabs, the second of each utterance of one step
+    (the tail loop again).  dw / dbias against float64, bit-equal across two runs"""
+    T, C, K = SLAB_T[B], 64, 3
     inputs, r64, r32 = _case(B, T, C, K)
     got = _run_gpu(inputs, B, T)
     _check(f"B {B}", got, r32, r64, names=("dw", "dbias"))
@@ -258,8 +265,8 @@ BRANCH_LENS = (20, 13, 1)
 @pytest.mark.parametrize("K", [3, 45])
 def test_cgmlp_branch_on_its_unfused_route(K, monkeypatch):
     """CgmlpBranch.fwd / bwd (tavsr/layer_blocks.py) at cgmlp_linear_units = 192: C = 96 is no multiple of the channel tile, so
-    csgu_usable is false and the branch runs LayerNorm + tavsr_dwconv_gate_fwd, and the generic backward (K = 45: past the 64 KB
-    request).  D = 64, utterances of (20, 13, 1) frames padded to T = 20 with the loss on the valid frames; output (valid frames),
+    csgu_usable is false and the branch runs LayerNorm + tavsr_dwconv_gate_fwd, and the backward without zr (the gate form of the
+    tile core at both K).  D = 64, utterances of (20, 13, 1) frames padded to T = 20 with the loss on the valid frames; output (valid frames),
     input gradient and every parameter gradient against oracle.leaves.ConvolutionalGatingMLP in float64"""
     from oracle import leaves as L
     from oracle.model import fill_parameters_, synth
