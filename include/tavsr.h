@@ -152,7 +152,14 @@ typedef struct tavsr_gemm_desc {
        x = h + m + l, and the six products hl, lh, mm, hm, mh, hh summed in that order into the fp32 accumulator: fp32-level
        error (the dropped ml, lm, ll are <= 2^-23 |a b|), another rounding than the fp32 MFMA's.  NaN in gives NaN out; +-inf in
        may give NaN (inf - inf in the split), and so may |x| > 0x1.fep127 (its high part rounds to inf).  Everywhere else the
-       bit is ignored and the fp32 B is read as before. */
+       bit is ignored and the fp32 B is read as before.
+       Bit 5 (value 32) is no position-major bit either (bits 4 and 5 alone count as zero for the above): conv_mode 2 with a_kmajor
+       and b_kmajor, conv_taps 9 (any stride) or 1, not 90: the weight gradient runs on v_mfma_f32_32x32x16_bf16 with BOTH
+       operands - dY and the image, activations both - split three ways in the kernel from the fp32 tiles the fp32 launch stages,
+       and the same six products summed in the same order (csrc/gemm_conv.hip, conv_x6_dw).  Operands, tiles, K slices, slabs,
+       tile orders and tavsr_gemm_ws are those of the launch without the bit; a_rowsum stays an fp32 sum, bit-identical with and
+       without the bit.  Error and NaN / inf behaviour as under bit 4.  Everywhere else (conv_mode 1, the unpadded window, the
+       stem's modes) the bit is ignored. */
   int32_t conv_mode, conv_H, conv_W, conv_C;
   const float* conv_zero;
   int32_t conv_stride, conv_taps;

@@ -302,6 +302,10 @@ template <int BM, int BN, int NT>
 struct SourceFor<2, false, BM, BN, NT, true, true> {
   using type = PairSource<PlainOperand<BM, true, NT, false>, PatchB<BN, NT>, BM>;
 };
+template <int BM, int BN, int NT>
+struct SourceFor<2, false, BM, BN, NT, true, true, true> {      // split operands (kConvX6Dw): the same two fp32 images, split in registers
+  using type = PairSource<PlainOperand<BM, true, NT, false>, PatchB<BN, NT>, BM>;
+};
 
 // CONV 2 + PM (conv_pm): K is the pixel axis and a K slice holds whole images (plan_conv), n of them from image i0 on.  The slice
 // is walked position-major: step k' covers pixel position k' / n (row-major, y * W + x) of image i0 + k' % n, so 32 consecutive
@@ -411,6 +415,10 @@ struct PatchWalkSource : SourceDefaults {
 };
 template <int BM, int BN, int NT>
 struct SourceFor<2, true, BM, BN, NT, true, true> {
+  using type = PatchWalkSource<BM, BN, NT>;
+};
+template <int BM, int BN, int NT>
+struct SourceFor<2, true, BM, BN, NT, true, true, true> {
   using type = PatchWalkSource<BM, BN, NT>;
 };
 
@@ -678,7 +686,7 @@ static int conv_wo(const tavsr_gemm_desc& d) { return (d.conv_W - 1) / std::max(
 constexpr int kPmStride2MaxPos = 36;
 static bool conv_pm(const tavsr_gemm_desc& d) {
   const bool stride_ok = d.conv_stride <= 1 || (d.conv_stride == 2 && (d.conv_posmajor & 8) && conv_ho(d) * conv_wo(d) <= kPmStride2MaxPos);
-  return (d.conv_posmajor & ~kConvX6) && (d.conv_mode == 1 || d.conv_mode == 2) && stride_ok && (d.conv_taps == 0 || d.conv_taps == 9) &&
+  return (d.conv_posmajor & ~(kConvX6 | kConvX6Dw)) && (d.conv_mode == 1 || d.conv_mode == 2) && stride_ok && (d.conv_taps == 0 || d.conv_taps == 9) &&
          (d.conv_mode == 2 || !d.a_rowsum);
 }
 
@@ -781,6 +789,21 @@ static bool conv_x6(const tavsr_gemm_desc& d, const Plan& p) {
          (d.conv_taps == 0 || d.conv_taps == 9 || (d.conv_taps == 1 && d.K >= 256)) && aligned16(d.B) && (int64_t)d.N * d.K * 6 < (1ll << 31);
 }
 
+// conv_posmajor's bit 5 applies: the weight gradient (conv_mode 2, both operands k-major) of the 9 padded taps, at stride 1 or 2, or
+// of the 1x1; not the unpadded window (conv_taps 90: Conv2dSubsampling keeps its launch) and no stem mode.  Both operands are
+// activations, so both are split in registers from the fp32 images the fp32 launch stages: same sources, same stage size, same
+// tiles, same K split, slabs and orders - only the K-step's arithmetic changes (gemm_glds.h, glds_tile).
+static bool conv_x6_dw(const tavsr_gemm_desc& d, const Plan&) {
+  return (d.conv_posmajor & kConvX6Dw) && d.conv_mode == 2 && d.a_kmajor && d.b_kmajor && (d.conv_taps == 0 || d.conv_taps == 9 || d.conv_taps == 1);
+}
+
+// the weight gradient's tile: what launch_conv runs and what tavsr_conv_dw_tile reports
+struct DwTile { int bm, bn, waves, x6; };
+static DwTile conv_dw_tile(const tavsr_gemm_desc& d, const Plan& p) {
+  const int x6 = conv_x6_dw(d, p);
+  return d.M % 128 == 0 ? DwTile{128, 64, 4, x6} : DwTile{64, 64, 4, x6};
+}
+
 int launch_conv(const tavsr_gemm_desc& d, const Plan& p, hipStream_t s) {
   switch (d.conv_mode) {
     case 1:       // A patches (NT / NN)
@@ -795,9 +818,13 @@ int launch_conv(const tavsr_gemm_desc& d, const Plan& p, hipStream_t s) {
       }
       if (p.nsplit == 1 && d.N % 128 == 0) return launch_conv_pm<64, 128, 3, false, false, 1>(d, p, s);
       return launch_conv_pm<64, 64, 5, false, false, 1>(d, p, s);
-    case 2:       // B patches (TN)
-      if (d.M % 128 == 0) return launch_conv_pm<128, 64, 3, true, true, 2>(d, p, s);
+    case 2: {     // B patches (TN)
+      const DwTile t = conv_dw_tile(d, p);
+      if (t.x6 && t.bm == 128) return launch_conv_pm<128, 64, 3, true, true, 2, true>(d, p, s);
+      if (t.x6) return launch_conv_pm<64, 64, 5, true, true, 2, true>(d, p, s);
+      if (t.bm == 128) return launch_conv_pm<128, 64, 3, true, true, 2>(d, p, s);
       return launch_conv_pm<64, 64, 5, true, true, 2>(d, p, s);
+    }
     case 4: return launch_conv_tile<64, 64, 5, false, false, 4, false>(d, p, s);      // Conv3d stem: 4-byte gathers
     case 5: return launch_conv_tile<64, 64, 5, true, true, 5, false>(d, p, s);
     case 6: return launch_conv_tile<64, 64, 5, false, false, 6, false>(d, p, s);      // Conv3d stem over padded clips: 16-byte chunks
@@ -905,6 +932,21 @@ extern "C" int tavsr_conv_dw_plan(int H, int W, int cin, int cout, int images, i
   const Plan p = plan_conv(d, true, force_split);
   out[0] = p.kchunk; out[1] = p.n_big; out[2] = p.kunit;
   return p.nsplit;
+}
+
+// The tile of that launch (conv_dw_tile) for any stride (1, 2) and taps (9, 1, 90): out = {block rows, block columns, waves, 1 where it
+// runs on split operands - conv_posmajor's bit 5 set and honoured}.  For tests, like the above.
+extern "C" int tavsr_conv_dw_tile(int H, int W, int cin, int cout, int images, int stride, int taps, int posmajor, int32_t* out) {
+  using namespace tavsr;
+  if (H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || images <= 0 || stride <= 0 || !out) return 0;
+  tavsr_gemm_desc d{};
+  d.conv_mode = 2; d.conv_H = H; d.conv_W = W; d.conv_C = cin; d.conv_stride = stride; d.conv_taps = taps; d.conv_posmajor = posmajor;
+  const int p0 = taps == 90 ? 1 : 0, nt = taps == 1 ? 1 : 9;
+  d.M = cout; d.N = nt * cin; d.K = images * ((H - 1 - 2 * p0) / stride + 1) * ((W - 1 - 2 * p0) / stride + 1);
+  d.a_kmajor = d.b_kmajor = 1; d.nb1 = d.nb2 = 1;
+  const DwTile t = conv_dw_tile(d, plan_conv(d, true, 0));
+  out[0] = t.bm; out[1] = t.bn; out[2] = t.waves; out[3] = t.x6;
+  return 1;
 }
 
 // ... and the order in which an XCD with ns slices of two lengths hands out their tiles (dw_xcd_order, then dw_tile_order):

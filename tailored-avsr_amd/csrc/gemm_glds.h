@@ -444,6 +444,8 @@ __device__ __forceinline__ uint32_t pk_bf16(float a, float b) {      // (bf16(a)
   f32x2 v = {a, b};
   return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2));
 }
+// (gemm_conv.hip is built with SLP vectorisation off, csrc/Makefile: left to itself hipcc pairs the neighbouring subtractions below into
+// v_pk_add_f32, which costs an MFMA gap far more than two v_sub_f32 do - profiles/r15_notes.md.  The same exact arithmetic either way.)
 __device__ __forceinline__ void split_pair(float a, float b, uint32_t& h, uint32_t& m, uint32_t& l) {
   h = pk_bf16(a, b);
   a -= __uint_as_float(h << 16);
@@ -569,6 +571,7 @@ struct PlainOperand {
 
 // The B operand as the three bf16 planes behind B [N][K] (kConvX6; the image is described at "split operands" above)
 constexpr int kConvX6 = 16;      // tavsr_gemm_desc.conv_posmajor, bit 4
+constexpr int kConvX6Dw = 32;    // ... bit 5: the weight gradient on split operands, both split in registers (gemm_conv.hip, conv_x6_dw)
 __device__ __forceinline__ const float* x6_planes(const tavsr_gemm_desc& d) { return d.B + (int64_t)d.N * d.K; }
 template <int ROWS, int NT>
 struct PlaneOperand {
@@ -599,7 +602,7 @@ struct PairSource : SourceDefaults {
 };
 
 template <int CONV, bool PM, int BM, int BN, int NT, bool AK, bool BKM, bool X6 = false>
-struct SourceFor;           // ::type, specialised next to each source (X6: B as bf16 planes, CONV 1 only)
+struct SourceFor;           // ::type, specialised next to each source (X6: CONV 1 with B as bf16 planes; CONV 2 with its fp32 sources)
 template <int BM, int BN, int NT, bool AK, bool BKM>
 struct SourceFor<0, false, BM, BN, NT, AK, BKM> {
   using type = PairSource<PlainOperand<BM, AK, NT, false>, PlainOperand<BN, BKM, NT, true>, BM>;
@@ -614,17 +617,20 @@ struct SourceFor<0, false, BM, BN, NT, AK, BKM> {
 // Two slice lengths (plan_conv, gemm_conv.hip): the first n_big slices are kunit longer; n_big = 0 everywhere else.
 // X6 (CONV 1 with both operands k-contiguous): the K-step runs on bf16 MFMAs over split operands ("split operands" above); the
 // stage's B image is then the three planes (BN * 192 bytes instead of BN * 128).
+// X6 with CONV 2 (weight gradient, both operands k-major): both operands are activations, so the stage holds the two fp32 k-major
+// images as without X6 and both are split in registers; the row sums stay fp32 in the fp32 path's association.
 template <int BM, int BN, int WM, int WN, int S, bool AK, bool BKM, int KW = 1, int CONV = 0, bool PM = false, bool X6 = false>
 __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, int nsplit, int tiles_n, int bid, bool vec_epi,
                                           int zidx, int n_big = 0, int kunit = 0) {
   constexpr int BK = kBK, NG = BK / 8;
   static_assert(NG % KW == 0, "k-groups must divide over the wave sets");
   static_assert(!PM || KW == 1, "position-major order: one wave set");
-  static_assert(!X6 || (CONV == 1 && !AK && !BKM && KW == 1), "split operands: CONV 1, both operands k-contiguous, one wave set");
+  static_assert(!X6 || (KW == 1 && ((CONV == 1 && !AK && !BKM) || (CONV == 2 && AK && BKM))),
+                "split operands: CONV 1 with both operands k-contiguous or CONV 2 with both k-major, one wave set");
   constexpr int NT = WM * WN * KW * 64;
   constexpr int TM = BM / WM / 32, TN = BN / WN / 32;
   using Src = typename SourceFor<CONV, PM, BM, BN, NT, AK, BKM, X6>::type;
-  constexpr int ASZ = BM * BK, STAGE = BM * BK + BN * (X6 ? kX6RowFloats : BK);
+  constexpr int ASZ = BM * BK, STAGE = BM * BK + BN * (X6 && !AK ? kX6RowFloats : BK);      // (the weight gradient's B stays an fp32 image)
   constexpr int G = Src::kDma;                  // LDS-DMA instructions per wave per tile
   static_assert((S - 2) * G <= 63, "vmcnt field");
   __shared__ __attribute__((aligned(1024))) float smem[S * STAGE];
@@ -672,7 +678,57 @@ __device__ __forceinline__ void glds_tile(const tavsr_gemm_desc& d, int kchunk, 
   auto compute = [&](int st) {
     const float* a_s = smem + st * STAGE;
     const float* b_s = a_s + ASZ;
-    if constexpr (X6) {
+    if constexpr (X6 && AK) {
+      // weight gradient: both operands are activations in the fp32 k-major images, both split here; the 8 values of a lane are
+      // k = 16b + 4 lk + {0..3} and + 8 for A and for B alike
+      float af[2][TM][8], bf[2][TN][8];
+      auto read_block = [&](int b, float (&fa)[TM][8], float (&fb)[TN][8]) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          float lo[4], hi[4];
+          read_frag_g<BM, true>(a_s, arow + i * 32, 2 * b, lk, lo);
+          read_frag_g<BM, true>(a_s, arow + i * 32, 2 * b + 1, lk, hi);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { fa[i][e] = lo[e]; fa[i][4 + e] = hi[e]; }
+        }
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+          float lo[4], hi[4];
+          read_frag_g<BN, true>(b_s, brow + j * 32, 2 * b, lk, lo);
+          read_frag_g<BN, true>(b_s, brow + j * 32, 2 * b + 1, lk, hi);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { fb[j][e] = lo[e]; fb[j][4 + e] = hi[e]; }
+        }
+      };
+      read_block(0, af[0], bf[0]);
+#pragma unroll
+      for (int b = 0; b < BK / 16; ++b) {
+        const int c = b & 1;
+        if (b + 1 < BK / 16) read_block(b + 1, af[c ^ 1], bf[c ^ 1]);
+        GEMM_SB();        // as below: the next block's fragment reads, then this block's splits and MFMAs
+        uint4 aq[TM][3], bq[TN][3];
+#pragma unroll
+        for (int i = 0; i < TM; ++i) split_frag(af[c][i], aq[i][0], aq[i][1], aq[i][2]);
+#pragma unroll
+        for (int j = 0; j < TN; ++j) split_frag(bf[c][j], bq[j][0], bq[j][1], bq[j][2]);
+#pragma unroll
+        for (int pr = 0; pr < 6; ++pr) {
+          constexpr int PA[6] = {0, 2, 1, 0, 1, 0}, PB[6] = {2, 0, 1, 1, 0, 0};
+#pragma unroll
+          for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j) acc[i][j] = mfma_bf16(aq[i][PA[pr]], bq[j][PB[pr]], acc[i][j]);
+        }
+        // the bias gradient stays fp32, in the fp32 path's association: one add per 8-k group, in group order (bit-identical)
+#pragma unroll
+        for (int i = 0; i < TM; ++i) {
+          asum[i] += (af[c][i][0] + af[c][i][1]) + (af[c][i][2] + af[c][i][3]);
+          asum[i] += (af[c][i][4] + af[c][i][5]) + (af[c][i][6] + af[c][i][7]);
+        }
+        GEMM_SB();
+      }
+      return;
+    } else if constexpr (X6) {
       float af[2][TM][8];
       uint4 bq[2][TN][3];
       auto read_block = [&](int b, float (&fa)[TM][8], uint4 (&qb)[TN][3]) {

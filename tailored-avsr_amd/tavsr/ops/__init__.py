@@ -97,6 +97,11 @@ CONV_TAPSKIP_STRIDE2_MAXPOS = 36
 # rounding than the fp32 MFMA's.  The weights are split once per step (ops.conv_wsplit), the activations in the kernel.
 # TAVSR_CONV_X6=0: the fp32 launches, bit-identical to what they were (A/B switch).
 CONV_X6 = os.environ.get("TAVSR_CONV_X6", "1") != "0"
+# The same for the weight gradient of these convolutions (bit 5 of conv_posmajor; csrc/gemm_conv.hip, conv_x6_dw): both operands are
+# activations, so both are split in the kernel, from the fp32 images the fp32 launch stages - same tiles, K split and orders.  A
+# switch of its own: CONV_X6 does not reach the weight gradient.  The bias gradient of the launch stays fp32, bit for bit.
+# TAVSR_CONV_X6_DW=0: the fp32 launches, bit-identical to what they were (A/B switch).
+CONV_X6_DW = os.environ.get("TAVSR_CONV_X6_DW", "1") != "0"
 
 # ---------------------------------------------------------------------------------------------- losses
 CTC_ALIGN_CHUNK = 16      # frames of emissions the alignment kernel gathers into LDS at a time (kAlignChunk, csrc/ctc.hip)

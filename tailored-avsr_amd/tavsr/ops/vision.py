@@ -13,7 +13,7 @@ from .matmul import gemm
 __all__ = ["conv1_fwd", "conv1_bwd", "im2col3x3s2", "col2im3x3s2_relu", "conv_out", "im2col2d", "col2im2d", "stem_implicit_ok",
            "stem_pad16_ok", "stem_pad", "stem_weight_288", "stem_weight_grad_from_288", "stem_conv_fwd_pad16", "stem_conv_dw_pad16",
            "stem_conv_fwd", "stem_conv_dw", "im2col_stem", "bn_stats", "rsqrt_eps", "bn_apply_fwd", "bn_bwd", "bn_bwd_pooled",
-           "maxpool3x3s2_fwd", "bn_act_maxpool3x3s2_fwd", "maxpool3x3s2_bwd", "avgpool_fwd", "avgpool_bwd", "conv_wflip", "conv_wsplit", "x6_takes", "_tapskip",
+           "maxpool3x3s2_fwd", "bn_act_maxpool3x3s2_fwd", "maxpool3x3s2_bwd", "avgpool_fwd", "avgpool_bwd", "conv_wflip", "conv_wsplit", "x6_takes", "x6_dw_takes", "_tapskip",
            "_tapskip2", "_tapskip_any", "conv3x3_fwd", "conv3x3_dx", "conv3x3_dw"]
 
 
@@ -274,6 +274,14 @@ def _x6(w, planes, taps=9, pad0=False):
     return (conv_wsplit(w) if planes is None else planes), 16
 
 
+def x6_dw_takes(cin, cout, taps=9, pad0=False, mode=2, pixels=0):
+    """does the split-operand kernel take the weight gradient of a convolution Cin -> Cout over ``pixels`` output pixels
+    (csrc/gemm_conv.hip, conv_x6_dw: conv_mode 2 with the 9 padded taps, at any stride, or the 1x1; not the unpadded window, not the
+    Conv3d stem's modes 5 / 7; whole K-steps of 32 pixels and column tiles inside one tap, as the implicit route needs)?  False where
+    ops.CONV_X6_DW is off."""
+    return bool(ops.CONV_X6_DW and mode == 2 and not pad0 and taps in (9, 1) and pixels % 32 == 0 and cin % 64 == 0)
+
+
 def _tapskip_bits():
     return 1 | (0 if ops.CONV_TILEORDER else 2) | (0 if ops.CONV_DW_UNEVEN else 4)
 
@@ -331,6 +339,7 @@ def conv3x3_dw(dz, x, H, W, stride=1, taps=9, pad0=False, bias_grad=False, force
     cin = x.shape[1]
     dw = empty(cout, taps * cin, like=dz)
     gb = empty(cout, like=dz) if bias_grad else None
+    x6 = 32 if x6_dw_takes(cin, cout, taps, pad0, pixels=M) else 0
     gemm(cout, taps * cin, M, dz, cout, x, cin, dw, taps * cin, a_kmajor=True, b_kmajor=True,
-         conv=(2, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0, dw=True)), a_rowsum=gb, force=force)
+         conv=(2, H, W, cin, stride, 90 if pad0 else taps, _tapskip_any(H, W, stride, taps, pad0, dw=True) | x6), a_rowsum=gb, force=force)
     return (dw, gb) if bias_grad else dw
