@@ -1459,6 +1459,38 @@ int tavsr_bootstrap_rates(const int32_t* dist, const int32_t* reflen, int32_t n,
                           tavsr_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Validation error rates on the device (csrc/editdist.hip): cer_ctc / cer / wer of espnet's ErrorCalculator
+ * (nets/e2e_asr_common.py; tavsr/models/espnet_model.py has the host restatement) from the argmax ids and the padded
+ * transcripts of a batch, one workgroup per utterance over the lattice core of tavsr_edit_distance, no host read.
+ *   tavsr_edit_distance_rows: dist[b] = Levenshtein distance (substitution, insertion, deletion cost 1) of the int32 rows
+ *       hyp[b][0 .. hyp_len[b]) and ref[b][0 .. ref_len[b]); rows b*ldh / b*ldr, lengths int32 [B] on the device, clamped to
+ *       [0, max_hyp] / [0, max_ref]; nothing beyond a length is read.  BOUND: max_ref <= 13652 (three diagonals of
+ *       max_ref + 1 words in 160 KiB of LDS), else TAVSR_EUNSUPPORTED; max_hyp is not bounded.
+ *   tavsr_error_counts: errs[k][b], ref_n[k][b] (int32 [n_modes][B], k counts the set bits of `modes` upwards) for
+ *       ys_hat [B][Th] (row stride ld_hat) against ys_pad [B][L] (ld_pad), int64 ids, -1 = padding.  Token v of text x is the
+ *       code points cps[span[x*(V+1) + v] .. span[x*(V+1) + v + 1]) (at most tok_max are read), x = 0 the token as it is, 1 with
+ *       space -> " " and blank -> "", 2 with space -> " "; cp_space[i] != 0: cps[i] is whitespace; drop[v] != 0: blank / space.
+ *       An id outside [0, V) contributes nothing.  Bits of `modes`:
+ *         1  ctc_chars: hypothesis = all Th ids, runs of equal ids collapsed, then ids with drop[] left out, text 0; reference =
+ *            ys_pad under the same filter (no collapse); symbols are code points; an empty reference gives errs = ref_n = 0.
+ *         2  att_chars: hypothesis = ids before ymax (the first -1 of the reference row, or L) in text 1, reference = every id
+ *            of the row in text 2, U+0020 left out of both; symbols are code points.
+ *         4  att_words: the same texts with U+0020 kept; symbols are words, the maximal runs of non-whitespace code points,
+ *            compared code point by code point (each word is numbered by the first identical word of the utterance).
+ *   tavsr_error_counts_ok: 1 when tavsr_error_counts takes the shape, else 0 (the entry then returns TAVSR_EUNSUPPORTED before
+ *       any launch).  BOUND, in 32-bit words of one workgroup's LDS, for every requested mode:
+ *         272 + capH + capR + 3 (capR + 1) [+ 3 ((capH + 1) / 2 + (capR + 1) / 2) for att_words] <= 40960,
+ *         capR = L * tok_max, capH = Th * tok_max (ctc_chars) or min(Th, L) * tok_max (att_*),
+ *       and B <= 2^24, Th, L <= 2^20, 1 <= tok_max <= 1024.  499 frames against 200 tokens of up to 9 code points: 11966 words.
+ * ------------------------------------------------------------------------------------------- */
+int tavsr_edit_distance_rows(const int32_t* hyp, int64_t ldh, const int32_t* hyp_len, int32_t max_hyp, const int32_t* ref, int64_t ldr,
+                             const int32_t* ref_len, int32_t max_ref, int32_t* dist, int32_t B, tavsr_stream_t stream);
+int tavsr_error_counts_ok(int32_t modes, int32_t B, int32_t Th, int32_t L, int32_t tok_max);
+int tavsr_error_counts(const int64_t* ys_hat, int64_t ld_hat, int32_t Th, const int64_t* ys_pad, int64_t ld_pad, int32_t L,
+                       const int32_t* span, const int32_t* cps, const uint8_t* cp_space, const uint8_t* drop, int32_t V, int32_t tok_max,
+                       int32_t modes, int32_t* errs, int32_t* ref_n, int32_t B, tavsr_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Batch assembly: the video pipeline of avsr_main.py:168-179 (src/transforms/video_transforms.py:59-147 +
  * torchvision RandomCrop / RandomHorizontalFlip) fused with the padding of src/utils/avsr_dataloader.py:102-142.
  *   tavsr_video_prep: dst[t][y][x], t < Tpad, of one clip: for t < T the source pixel

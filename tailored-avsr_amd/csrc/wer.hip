@@ -9,7 +9,7 @@
 //   * bootstrap: one workgroup per resample draws n sentence indices (Philox counter = (resample, position)) and sums
 //     their distances and reference lengths; the reference's rand() stream (seeded with time(0)) is not reproducible,
 //     so parity here is statistical.
-#include "common.h"
+#include "editdist.h"
 
 namespace tavsr {
 
@@ -18,32 +18,11 @@ constexpr int kEditMaxLen = 4095;     // symbols per sequence (tasas reads lines
 __global__ __launch_bounds__(256) void edit_distance_kernel(const int32_t* __restrict__ ref, const int64_t* __restrict__ ref_off,
                                                             const int32_t* __restrict__ hyp, const int64_t* __restrict__ hyp_off,
                                                             int32_t* __restrict__ dist) {
-  __shared__ int32_t diag[3][kEditMaxLen + 1];
+  __shared__ int32_t diag[3 * (kEditMaxLen + 1)];
   const int p = blockIdx.x;
-  const int32_t* r = ref + ref_off[p];
-  const int32_t* h = hyp + hyp_off[p];
   const int Lr = (int)(ref_off[p + 1] - ref_off[p]), Lh = (int)(hyp_off[p + 1] - hyp_off[p]);
-  // D[i][j], i symbols of the reference against j of the hypothesis; diagonal k holds D[i][k - i] at index i
-  int a = 0, b = 1, c = 2;             // diagonals k - 2, k - 1, k
-  if (threadIdx.x == 0) diag[b][0] = 0;            // k = 0: D[0][0]
-  __syncthreads();
-  for (int k = 1; k <= Lr + Lh; ++k) {
-    const int lo = max(0, k - Lh), hi = min(Lr, k);
-    for (int i = lo + threadIdx.x; i <= hi; i += 256) {
-      const int j = k - i;
-      int v;
-      if (i == 0) v = j;
-      else if (j == 0) v = i;
-      else {
-        const int sub = diag[a][i - 1] + (r[i - 1] != h[j - 1] ? 1 : 0);
-        v = min(sub, min(diag[b][i - 1], diag[b][i]) + 1);
-      }
-      diag[c][i] = v;
-    }
-    __syncthreads();
-    const int t = a; a = b; b = c; c = t;
-  }
-  if (threadIdx.x == 0) dist[p] = diag[b][Lr];
+  const int d = edit_distance_core(ref + ref_off[p], Lr, hyp + hyp_off[p], Lh, diag, kEditMaxLen + 1);
+  if (threadIdx.x == 0) dist[p] = d;
 }
 
 // rates[it] = 100 * sum_x dist[idx(it, x)] / sum_x reflen[idx(it, x)],  idx uniform on [0, n)

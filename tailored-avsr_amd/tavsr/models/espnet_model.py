@@ -44,16 +44,113 @@ def _levenshtein(a, b) -> int:
     return prev[-1]
 
 
+def _separable(tokens, sym) -> bool:
+    """Does ``"".join(tokens of any id sequence).replace(sym, x)`` equal the join of the per-token ``replace``?  A sufficient
+    condition: ``sym`` is one character, or no token other than ``sym`` itself contains it and no token (``sym`` included) ends
+    in a non-empty proper prefix of it - then no occurrence of ``sym`` in a joined string can cross a token boundary."""
+    if not sym:
+        return False
+    if len(sym) == 1:
+        return True
+    prefixes = tuple(sym[:k] for k in range(1, len(sym)))
+    return not any((sym in t and t != sym) or t.endswith(prefixes) for t in tokens)
+
+
+def error_tables(char_list, sym_space, sym_blank):
+    """The token tables of ``tavsr_error_counts`` (include/tavsr.h) on the host, or None where ``_separable`` does not hold for
+    ``sym_space`` on the tokens or for ``sym_blank`` on the tokens after the space replacement.  ``texts``: per token (0) the
+    token, (1) what the hypothesis of ``ErrorCalculator.__call__`` makes of it (space -> " ", then blank -> "") and (2) what
+    the reference makes of it (space -> " "); ``span`` int32 [3 * (V + 1)], ``cps`` int32 and ``cp_space`` uint8 (``str.isspace``
+    of each code point), ``drop`` uint8 [V] (blank / space: left out by ``cer_ctc``), ``tok_max``: the longest text."""
+    raw = list(char_list)
+    if not _separable(raw, sym_space):
+        return None
+    ref = [t.replace(sym_space, " ") for t in raw]
+    if not _separable(ref, sym_blank):
+        return None
+    texts = (raw, [t.replace(sym_blank, "") for t in ref], ref)
+    span, chars = [], []
+    for text in texts:
+        for t in text:
+            span.append(len(chars))
+            chars.extend(t)
+        span.append(len(chars))
+    chars.append("\0")      # a table of empty tokens still has an address
+    return dict(texts=texts, span=torch.tensor(span, dtype=torch.int32), cps=torch.tensor([ord(c) for c in chars], dtype=torch.int32),
+                cp_space=torch.tensor([c.isspace() for c in chars], dtype=torch.uint8),
+                drop=torch.tensor([t in (sym_blank, sym_space) for t in raw], dtype=torch.uint8),
+                tok_max=max(1, max(len(t) for text in texts for t in text)))
+
+
 class ErrorCalculator:
-    """CER/WER of espnet.nets.e2e_asr_common.ErrorCalculator on id sequences (host side, eval only)."""
+    """CER/WER of espnet.nets.e2e_asr_common.ErrorCalculator on id sequences (eval only).
+
+    Two routes compute the same integers.  The host route joins the token strings and runs ``_levenshtein`` in Python.  The
+    device route (``ops.error_counts``, csrc/editdist.hip) reads nothing on the host; it is taken when the inputs are CUDA
+    tensors, ``ops.DEVICE_ERROR_RATES`` is on, the token tables exist and ``ops.error_counts_ok`` takes the shape.  The tables
+    hold per-token texts, so they exist only where replacing ``sym_space`` / ``sym_blank`` per token equals the host's replace on
+    the joined string: ``_separable`` states the sufficient condition that is checked, and a calculator whose token list fails
+    it stays on the host route for good.  An id outside the token list, which the host route raises on (or wraps, when
+    negative and not -1), contributes nothing on the device route.
+
+    The host route returns Python floats, ``None`` for ``cer_ctc`` over empty references, and raises ``ZeroDivisionError`` for
+    ``cer`` / ``wer`` over empty references.  The device route returns 0-dim float64 device tensors, ``errs.sum() / ref_n.sum()`` in
+    double, whose ``float()`` has the bits of the host's division; in the two empty-reference cases it returns NaN."""
+
+    MODES = {"ctc_chars": 1, "att_chars": 2, "att_words": 4}      # the bits of tavsr_error_counts' `modes`
 
     def __init__(self, char_list, sym_space, sym_blank, report_cer=False, report_wer=False):
         self.char_list, self.space, self.blank = char_list, sym_space, sym_blank
         self.report_cer, self.report_wer = report_cer, report_wer
         self.idx_blank = char_list.index(sym_blank)
         self.idx_space = char_list.index(sym_space) if sym_space in char_list else None
+        self.host_tables = error_tables(char_list, sym_space, sym_blank)
+        self._device_tables = {}
+
+    def _tables(self, ys_hat, ys_pad, modes):
+        """the device route's tables for this call, or None: the host route"""
+        if not (ops.DEVICE_ERROR_RATES and ys_hat.is_cuda and ys_pad.is_cuda and self.host_tables is not None):
+            return None
+        h = self.host_tables
+        if not ops.error_counts_ok(modes, ys_hat.shape[0], ys_hat.shape[1], ys_pad.shape[1], h["tok_max"]):
+            return None
+        tb = self._device_tables.get(ys_hat.device)
+        if tb is None:      # once per device
+            tb = self._device_tables[ys_hat.device] = ops.ErrorTables(
+                *(h[k].to(ys_hat.device) for k in ("span", "cps", "cp_space", "drop")), len(self.char_list), h["tok_max"])
+        return tb
+
+    @staticmethod
+    def _rate(errs, ref_n):
+        e, n = errs.sum().double(), ref_n.sum().double()
+        return (e / n).masked_fill(n == 0, float("nan"))
+
+    def counts(self, ys_hat, ys_pad, mode):
+        """(errs [B], ref_n [B]) int32 of ``mode`` ("ctc_chars", "att_chars", "att_words"): per utterance the edit count and the
+        reference length that ``cer_ctc`` / ``cer`` / ``wer`` sum over the batch, for callers that sum over a corpus.  On the
+        device where the device route takes the call, else on the host."""
+        tb = self._tables(ys_hat, ys_pad, self.MODES[mode])
+        if tb is not None:
+            errs, ref_n = ops.error_counts(ys_hat, ys_pad, tb, self.MODES[mode])
+            return errs[0], ref_n[0]
+        pairs = []
+        for y, ref in zip(ys_hat.tolist(), ys_pad.tolist()):
+            if mode == "ctc_chars":
+                keep = lambda i: i != -1 and i != self.idx_blank and i != self.idx_space
+                h = "".join(self.char_list[i] for i, _ in groupby(y) if keep(i))
+                r = "".join(self.char_list[i] for i in ref if keep(i))
+            else:
+                ymax = ref.index(-1) if -1 in ref else len(ref)
+                h = "".join(self.char_list[i] for i in y[:ymax]).replace(self.space, " ").replace(self.blank, "")
+                r = "".join(self.char_list[i] for i in ref if i != -1).replace(self.space, " ")
+                h, r = (h.split(), r.split()) if mode == "att_words" else (h.replace(" ", ""), r.replace(" ", ""))
+            pairs.append((_levenshtein(h, r) if (r or mode != "ctc_chars") else 0, len(r)))
+        return tuple(torch.tensor(c, dtype=torch.int32) for c in (zip(*pairs) if pairs else ((), ())))
 
     def cer_ctc(self, ys_hat, ys_pad):
+        tb = self._tables(ys_hat, ys_pad, self.MODES["ctc_chars"])
+        if tb is not None:
+            return self._rate(*ops.error_counts(ys_hat, ys_pad, tb, self.MODES["ctc_chars"]))
         errs, n = 0, 0
         for y, ref in zip(ys_hat.tolist(), ys_pad.tolist()):
             keep = lambda i: i != -1 and i != self.idx_blank and i != self.idx_space
@@ -69,6 +166,12 @@ class ErrorCalculator:
     def __call__(self, ys_hat, ys_pad, is_ctc=False):
         if is_ctc:
             return self.cer_ctc(ys_hat, ys_pad)
+        modes = (self.MODES["att_chars"] if self.report_cer else 0) | (self.MODES["att_words"] if self.report_wer else 0)
+        tb = self._tables(ys_hat, ys_pad, modes) if modes else None
+        if tb is not None:      # cer and wer of the batch in one launch
+            errs, ref_n = ops.error_counts(ys_hat, ys_pad, tb, modes)
+            rates = [self._rate(errs[k], ref_n[k]) for k in range(errs.shape[0])]
+            return (rates.pop(0) if self.report_cer else None), (rates.pop(0) if self.report_wer else None)
         hyps, refs = [], []
         for y, ref in zip(ys_hat.tolist(), ys_pad.tolist()):
             ymax = ref.index(-1) if -1 in ref else len(ref)
@@ -226,7 +329,7 @@ class ESPnetASRModel(torch.nn.Module):
                 cer_ctc = None
                 if not self.training and self.error_calculator is not None:
                     ys_hat = self.ctc.argmax(encoder_out).data
-                    cer_ctc = self.error_calculator(ys_hat.cpu(), text.cpu(), is_ctc=True)
+                    cer_ctc = self.error_calculator(ys_hat, text, is_ctc=True)
                 stats["loss_ctc"], stats["cer_ctc"] = loss_ctc.detach(), cer_ctc
             if self.interctc_weight != 0.0 and intermediate_outs is not None:      # espnet_model.py:260-304
                 if self.aux_ctc is not None:
@@ -237,7 +340,7 @@ class ESPnetASRModel(torch.nn.Module):
                     cer_ic = None
                     if not self.training and self.error_calculator is not None:
                         ys_hat = self.ctc.argmax(intermediate_out).data
-                        cer_ic = self.error_calculator(ys_hat.cpu(), text.cpu(), is_ctc=True)
+                        cer_ic = self.error_calculator(ys_hat, text, is_ctc=True)
                     loss_interctc = loss_ic if loss_interctc is None else F_.WeightedSumFn.apply(loss_interctc, loss_ic, 1.0, 1.0)
                     stats[f"loss_interctc_layer{layer_idx}"] = loss_ic.detach()
                     stats[f"cer_interctc_layer{layer_idx}"] = cer_ic
@@ -275,7 +378,7 @@ class ESPnetASRModel(torch.nn.Module):
             acc_att = _Accuracy(correct)
             if not self.training and self.error_calculator is not None:
                 ids, _, _ = ops.ctc_greedy(decoder_out.detach().contiguous(), None, -1, collapse=False)  # argmax(-1)
-                cer_att, wer_att = self.error_calculator(ids.cpu(), text.cpu())
+                cer_att, wer_att = self.error_calculator(ids, text)
         return loss_att, {"loss_att": loss_att.detach() if loss_att is not None else None, "acc": acc_att, "cer": cer_att,
                           "wer": wer_att}
 

@@ -105,6 +105,9 @@ CONV_X6_DW = os.environ.get("TAVSR_CONV_X6_DW", "1") != "0"
 
 # ---------------------------------------------------------------------------------------------- losses
 CTC_ALIGN_CHUNK = 16      # frames of emissions the alignment kernel gathers into LDS at a time (kAlignChunk, csrc/ctc.hip)
+# Validation CER / WER on the device (csrc/editdist.hip; ErrorCalculator in models/espnet_model.py picks the route per call).
+# TAVSR_DEVICE_ERROR_RATES=0: the host route, ids copied to the host and a Python edit distance (A/B switch; the same integers).
+DEVICE_ERROR_RATES = os.environ.get("TAVSR_DEVICE_ERROR_RATES", "1") != "0"
 
 # ---------------------------------------------------------------------------------------------- data
 RESAMPLE_ROLLOFF, RESAMPLE_ZEROS, RESAMPLE_BETA = 0.9475937167399596, 64, 14.769656459379492      # "kaiser_best" filter constants

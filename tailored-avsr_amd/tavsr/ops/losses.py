@@ -1,6 +1,8 @@
 """CTC (loss, greedy, forced alignment), Mask-CTC, label smoothing, the LM's shifted rows and the embeddings."""
 from __future__ import annotations
 
+from collections import namedtuple
+
 import torch
 
 from .. import _lib as L
@@ -8,8 +10,8 @@ from .._lib import check, lib, ptr, require_cuda, stream
 from .base import empty, f32
 from .rng import _new_token
 
-__all__ = ["ctc_loss", "ctc_greedy", "ctc_align_lds_ok", "ctc_align", "maskctc_init", "maskctc_step", "mask_uniform", "count_recip",
-           "lm_shift", "row_sums", "lsm_loss", "embed_pe", "embed_bwd"]
+__all__ = ["ctc_loss", "ctc_greedy", "ctc_align_lds_ok", "ctc_align", "edit_distance_rows", "ErrorTables", "error_counts_ok", "error_counts",
+           "maskctc_init", "maskctc_step", "mask_uniform", "count_recip", "lm_shift", "row_sums", "lsm_loss", "embed_pe", "embed_bwd"]
 
 
 # ---------------------------------------------------------------------------------------------- CTC / losses
@@ -73,6 +75,52 @@ def ctc_align(logits, hlens, targets, tlens, blank=0, rows=None, route=None):
                                 max(targets.stride(0), Lmax), ptr(tlens), int(blank), ptr(align), ptr(frame_lp), ptr(span),
                                 ptr(score), ptr(ws), N, T, V, Lmax, stream()), "tavsr_ctc_align")
     return align, frame_lp, span, score
+
+
+# ---------------------------------------------------------------------------------------------- error rates
+def edit_distance_rows(hyp, hyp_len, ref, ref_len):
+    """Levenshtein distances of B pairs of padded symbol rows (tavsr_edit_distance_rows): hyp [B, n], ref [B, m] int32 (views of
+    wider buffers are taken as they are), hyp_len / ref_len int32 [B] on the device -> dist int32 [B].  Nothing beyond a length
+    is read.  (``ops.edit_distance`` is the packed-offsets form of the corpus evaluator.)"""
+    require_cuda(hyp, hyp_len, ref, ref_len)
+    B, n = hyp.shape
+    m = ref.shape[1]
+    assert ref.shape[0] == B and hyp.dtype == ref.dtype == torch.int32 and (n <= 1 or hyp.stride(1) == 1) and (m <= 1 or ref.stride(1) == 1)
+    assert all(t.dtype == torch.int32 and t.shape == (B,) and t.is_contiguous() for t in (hyp_len, ref_len))
+    dist = torch.empty((B,), dtype=torch.int32, device=hyp.device)
+    check(lib().tavsr_edit_distance_rows(ptr(hyp), max(hyp.stride(0), n) if B > 1 else n, ptr(hyp_len), n, ptr(ref),
+                                         max(ref.stride(0), m) if B > 1 else m, ptr(ref_len), m, ptr(dist), B, stream()),
+          "tavsr_edit_distance_rows")
+    return dist
+
+
+ErrorTables = namedtuple("ErrorTables", "span cps cp_space drop V tok_max")      # device tensors of tavsr_error_counts' token tables
+
+
+def error_counts_ok(modes, B, Th, L, tok_max) -> bool:
+    """does tavsr_error_counts take this shape?  the library's answer (tavsr_error_counts_ok; include/tavsr.h states the bound)"""
+    return bool(lib().tavsr_error_counts_ok(int(modes), int(B), int(Th), int(L), int(tok_max)))
+
+
+def error_counts(ys_hat, ys_pad, tables, modes):
+    """ys_hat [B, Th], ys_pad [B, L] int64 ids (-1 = padding), ``tables``: an ``ErrorTables``, ``modes``: bits 1 ctc_chars,
+    2 att_chars, 4 att_words -> (errs, ref_n) int32 [n_modes, B], one row per set bit in rising order: the edit count and the
+    reference length of every utterance (tavsr_error_counts, one launch).  No host read, no sync: capturable."""
+    require_cuda(ys_hat, ys_pad, *tables[:4])
+    if ys_hat.dtype != torch.int64 or (ys_hat.shape[1] > 1 and ys_hat.stride(1) != 1):
+        ys_hat = ys_hat.to(torch.int64).contiguous()
+    if ys_pad.dtype != torch.int64 or (ys_pad.shape[1] > 1 and ys_pad.stride(1) != 1):
+        ys_pad = ys_pad.to(torch.int64).contiguous()
+    (B, Th), L = ys_hat.shape, ys_pad.shape[1]
+    assert ys_pad.shape[0] == B and tables.span.numel() == 3 * (tables.V + 1) and tables.drop.numel() == tables.V
+    n_modes = bin(int(modes)).count("1")
+    errs = torch.empty((n_modes, B), dtype=torch.int32, device=ys_hat.device)
+    ref_n = torch.empty((n_modes, B), dtype=torch.int32, device=ys_hat.device)
+    check(lib().tavsr_error_counts(ptr(ys_hat), max(ys_hat.stride(0), Th) if B > 1 else Th, Th, ptr(ys_pad),
+                                   max(ys_pad.stride(0), L) if B > 1 else L, L, ptr(tables.span), ptr(tables.cps), ptr(tables.cp_space),
+                                   ptr(tables.drop), tables.V, tables.tok_max, int(modes), ptr(errs), ptr(ref_n), B, stream()),
+          "tavsr_error_counts")
+    return errs, ref_n
 
 
 def maskctc_init(logits, hlens, blank, mask_token, threshold, n_iterations):

@@ -467,16 +467,23 @@ def training(e2e, train_loader, optimizer, scheduler, accum_grad, device="cuda",
 
 
 def validation(e2e, data_loader, device="cuda"):
-    """avsr_main.py:60-82: mean loss and mean CTC character error rate (%) over the loader, rounded to 3 decimals."""
+    """avsr_main.py:60-82: mean loss and mean CTC character error rate (%) over the loader, rounded to 3 decimals.  Where the
+    model hands back the loss and ``cer_ctc`` as device tensors (the device route of ``ErrorCalculator``) both running sums stay
+    on the device in float64 and are read once after the loop: the same IEEE doubles added in the same order as the host sums."""
     e2e.eval()
-    data_loss, data_cer = 0.0, 0.0
+    data_loss, data_cer = 0.0, 0.0      # Python floats, or 0-dim float64 device tensors from the first device batch on
     with torch.no_grad():
         for batch in data_loader:
             batch = _to_device(batch, device)
             loss, stats, weight = e2e(**batch)
-            data_loss += float(loss)
-            data_cer += float(stats["cer_ctc"]) * 100.0
-    return round(data_loss / len(data_loader), 3), round(data_cer / len(data_loader), 3)
+            cer = stats["cer_ctc"]
+            if torch.is_tensor(loss) and loss.is_cuda and torch.is_tensor(cer) and cer.is_cuda:
+                data_loss = data_loss + loss.double().reshape(())
+                data_cer = data_cer + cer.double().reshape(()) * 100.0
+            else:
+                data_loss += float(loss)
+                data_cer += float(cer) * 100.0
+    return round(float(data_loss) / len(data_loader), 3), round(float(data_cer) / len(data_loader), 3)
 
 
 def lm_training(lm, train_loader, optimizer, scheduler, accum_grad, device="cuda", grad_clip=-1.0, grad_clip_type=2.0):
